@@ -20,7 +20,9 @@ Prints ONE JSON line on rank 0 (fields: see the driver contract), including
                  timings of the launches inside the timed region (`kernel_ms`; under the N > 1 schedule, where two launches
                  co-run on the two render streams, the union of the launch intervals per launch, with the plain mean of
                  the event pairs beside it as `kernel_ms_event_pairs`); `clock_ghz` = the shader clock under load read inside
-                 the kernel (s_memtime / s_memrealtime): the launch is power-bound, the 2.5 PF peak assumes 2.4 GHz;
+                 the kernel (s_memtime / s_memrealtime): the launch is power-bound, the 2.5 PF peak assumes 2.4 GHz.
+A plain run stops there: set-up, W warm-up steps, the K timed steps, the line.  `--full` adds everything below (each still
+switched off by its own --no-* option), and for N > 1 the gather check and the collective timed alone (`gather.ms_alone`):
   sustained    - the same step repeated for >= --sustain-seconds (default 10 s) after the K timed steps: the K steps
                  the driver asks for last well under a second, the chip's DVFS settles later;
   cpu_baseline - the oracle (oracle/dfa_oracle.py, a port of the reference's CPU path) timed on a bounded
@@ -37,6 +39,11 @@ Prints ONE JSON line on rank 0 (fields: see the driver contract), including
                  head / composite), the worst frame, the gate "within 0.05 dB" implies for a 30-dB model;
   parity_check - (N == 1) after the timed loops, 64 rays of the LAST timed frame rendered again in the timed configuration
                  and compared with the CPU oracle (outside the timed region): binds the timed launch to the parity suite.
+
+`--dump-outputs DIR` writes what the last of the K timed steps computed, as a caller of the timed path receives it, to
+DIR/<name>.npy (float32; rank 0): the frame workloads their images (`rgb_head`, and `rgb_com` for two fields; [H*W, 3], or
+[8, H*W, 3] for the c5 batch), the training workloads the step's losses and rendered rays and the decoder's parameters after
+its optimizer step.  The inputs are seeded: the same arguments give the same inputs on every run.
 
 `python bench.py --gpus N` (N > 1) without a torchrun environment launches its own N ranks (torch.distributed.run on
 127.0.0.1, a probed free port) - the driver's plain `python bench.py --gpus 8` and the torchrun form give the same run.
@@ -81,7 +88,7 @@ WORKLOADS = {
 TRAIN_WORKLOADS = ("c4", "c4s", "c4h")
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)        # 300 frames = ~10 s: a sustained number by default
@@ -92,16 +99,41 @@ def parse():
     ap.add_argument("--tier", default="f16", choices=["f16", "bf16", "f32"])
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample (after the sweep)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0,
-                    help="length of the sustained run after the K timed steps (0 = off; skipped when the K steps "
-                         "themselves already lasted that long)")
+    ap.add_argument("--sustain-seconds", type=float, default=None,
+                    help="length of the sustained run after the K timed steps (default: 10 with --full, 0 = off without; "
+                         "skipped when the K steps themselves already lasted that long)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline figure: sustained run, CPU baseline, other workloads (N == 1), "
+                         "parity check, f16 guards, power ceiling; N > 1: gather check, the collective timed alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MiB in all)")
     ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other workloads (N == 1)")
     ap.add_argument("--size", type=int, default=450, choices=[450, 512],
                     help="frame size of the render workloads (512 = what scripts/process_data.sh emits; the counter passes of "
                          "`c2_512` in profiles/traffic.json use it)")
     ap.add_argument("--no-parity-check", action="store_true", help="skip the 64-ray oracle check after the timed loops (N == 1)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)      # internal: one process of cpu_baseline.multi_process
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 10.0 if args.full else 0.0
+    return args
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  Past DUMP_LIMIT bytes in all, an array is cut to a fixed,
+    seeded sample of its rows (of its last axis' vectors), the same rows on every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for k, v in arrays.items():
+        if total > DUMP_LIMIT and v.ndim > 0 and v.size > 1:
+            rows = v.reshape(-1, v.shape[-1]) if v.ndim > 1 else v
+            keep = max(1, int(len(rows) * DUMP_LIMIT // total))
+            v = rows[np.sort(np.random.RandomState(0).choice(len(rows), keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -240,7 +272,7 @@ def cpu_worker(spec):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-def bench_training(args, workload, steps, warmup, world, rank, dev, sustain_s=0.0, tier=None):
+def bench_training(args, workload, steps, warmup, world, rank, dev, sustain_s=0.0, tier=None, dump=False):
     """configs[3]: one optimisation step per `step`: signals -> fold -> fused HIP forward (recorder on) -> MSE
     losses -> HIP backward (compositing, dX chain, weight-gradient GEMMs) -> flat-bucket all_reduce -> gated Adams.
     Ground-truth frames and background are resident uint8 device tensors; pixels are drawn and targets gathered on
@@ -312,8 +344,11 @@ def bench_training(args, workload, steps, warmup, world, rank, dev, sustain_s=0.
         mark("start")
         img_i = int(rng_frame.randint(0, 8))
         pix = sampler.draw()
-        loss, *_ = run_nerf.train_step_loss_hip(mods, ds, 0, img_i, pix, gt[img_i][0], gt[img_i][1], zs, za, gstep, a,
-                                                8, embed_fn, ds[0]["poses"][0], buf)
+        res = run_nerf.train_step_loss_hip(mods, ds, 0, img_i, pix, gt[img_i][0], gt[img_i][1], zs, za, gstep, a,
+                                           8, embed_fn, ds[0]["poses"][0], buf)
+        loss = res[0]
+        if dump:
+            state["res"] = res                   # (--dump-outputs: what the step hands its caller, read after the timed steps)
         mark("fwd")
         t1 = c()
         for o in opts.values():
@@ -369,6 +404,12 @@ def bench_training(args, workload, steps, warmup, world, rank, dev, sustain_s=0.
     if phases is not None:
         phases.clear()
     dt = timed(steps)
+    if dump and rank == 0:
+        # what the last timed step hands its caller (loss = loss_head + loss_com, the two losses, the rendered rays of both
+        # fields) and what it leaves behind: the decoder's parameters after the step's optimizer update
+        dumped = {k: v.detach().float().cpu().numpy()
+                  for k, v in zip(("loss", "loss_head", "loss_com", "rgb_head", "rgb_com"), state["res"])}
+        dumped["decoder_params"] = torch.cat([p.detach().float().reshape(-1) for p in mods["decoder"].parameters()]).cpu().numpy()
     if phases is not None and rank == 0:
         acc, n4 = {}, len(phases) // 4
         for k in range(1, n4):                       # (skip the first step)
@@ -445,6 +486,8 @@ def bench_training(args, workload, steps, warmup, world, rank, dev, sustain_s=0.
             out["sustained"] = sus
         if os.environ.get("DFN_BENCH_PRINT_LOSS"):      # (tests: the loss of the last timed step, rank 0)
             out["last_loss"] = state["loss"]
+        if dump:
+            out["_dump"] = dumped
     return out
 
 
@@ -556,7 +599,8 @@ def power_ceiling(pk, tier, dev, kernel_tflops):
     return res
 
 
-def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_s=0.0, check=False, size=450):
+def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_s=0.0, check=False, size=450, full=False,
+                 dump=False):
     from dfanerf import engine, nets, synth
     from dfanerf._lib import check as chk, lib
     n_fine, fields, desc = WORKLOADS[workload]
@@ -732,6 +776,12 @@ def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_
         torch.cuda.synchronize()
         return {"frame": f, "identical": bool(torch.equal(got, whole)), "max_abs_diff": float((got - whole).abs().max())}
 
+    def images(img):
+        """the images of a step as its caller receives them (N > 1: as rank 0 gathered them): {name: [B, R, 3]}, [R, 3] for
+        one frame per step"""
+        v = img.view(-1, B, n_img, per, 3).permute(1, 2, 0, 3, 4).reshape(B, n_img, -1, 3)[:, :, :R].cpu().numpy()
+        return {name: (v[:, j] if B > 1 else v[0, j]) for j, name in enumerate(("rgb_head", "rgb_com")[:n_img])}
+
     def clock():
         """effective shader clock of the last launch (GHz), read inside the kernel"""
         c = probe.cpu().numpy()
@@ -743,6 +793,7 @@ def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_
     try:
         dt, kern_ms, dt_rank = timed(steps, warmup)
         pair_ms = state["pair_ms"]
+        dumped = images(state["last"][1]) if dump and rank == 0 else None
         ghz = clock()
         sus = None
         if sustain_s > 0 and dt < sustain_s:
@@ -756,14 +807,14 @@ def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_
     rank_ms = all_ranks(dt_rank / steps * 1e3, world, dev)
     rank_kern = all_ranks(kern_ms, world, dev)
     gcheck = None
-    if multi and rank == 0:
+    if multi and rank == 0 and full:
         try:
             gcheck = gather_check()
         except Exception as e:                          # never lose the line to the check; the failure is in the line
             gcheck = {"error": f"{type(e).__name__}: {e}"}
     # the collective alone (nothing to overlap with): 20 gathers of the step's shard, synchronised
     gather_ms = None
-    if multi:
+    if multi and full:
         torch.cuda.synchronize()
         dist.barrier()
         t0 = time.perf_counter()
@@ -887,6 +938,8 @@ def bench_render(args, workload, tier, steps, warmup, world, rank, dev, sustain_
         except Exception as e:                      # never lose the headline line to the check; the failure is in the line
             out["parity_check"] = {"error": f"{type(e).__name__}: {e}"}
     out["_scene"] = (sc, st, zs, za, n_fine, fields)
+    if dumped is not None:
+        out["_dump"] = dumped
     return out
 
 
@@ -981,14 +1034,15 @@ def main():
     run_all = args.workload == "all"
     headline = "c2" if run_all else args.workload
     train_wl = headline in TRAIN_WORKLOADS
+    dump = bool(args.dump_outputs)
     if train_wl:
-        out = bench_training(args, headline, args.steps, args.warmup, world, rank, dev, args.sustain_seconds)
+        out = bench_training(args, headline, args.steps, args.warmup, world, rank, dev, args.sustain_seconds, dump=dump)
     else:
-        out = bench_render(args, headline, args.tier, args.steps, args.warmup, world, rank, dev,
-                           args.sustain_seconds, check=not args.no_parity_check, size=args.size)
+        out = bench_render(args, headline, args.tier, args.steps, args.warmup, world, rank, dev, args.sustain_seconds,
+                           check=args.full and not args.no_parity_check, size=args.size, full=args.full, dump=dump)
     extra = {}
     multi = world > 1 or dist.is_initialized()
-    if (world == 1 and not args.no_extra) or run_all:
+    if (world == 1 and args.full and not args.no_extra) or run_all:
         # the other BASELINE configs, short runs in the same process (driver-timed, not builder-only numbers); c2_f32 = the
         # exact tier, the one that meets the north star's "within 1e-4 PSNR" clause.  Under a process group (--workload all
         # at N > 1, or DFN_BENCH_RCCL_WORLD1) every rank runs the same list in the same order; a workload that raises on a
@@ -1012,7 +1066,7 @@ def main():
                     r = bench_training(args, wl, k, w, world, rank, dev, tier="f32" if name == "c4_f32" else None)
                 else:
                     r = bench_render(args, wl, tier, k, w, world, rank, dev, size=512 if name == "c2_512" else 450,
-                                     check=(name == "c2_f32" and not args.no_parity_check))
+                                     check=(name == "c2_f32" and args.full and not args.no_parity_check), full=args.full)
             except Exception as e:                      # never lose the headline line to a side measurement
                 err = f"{type(e).__name__}: {e}"
             if world > 1:
@@ -1037,9 +1091,12 @@ def main():
             print(f"bench.py: workload {name}: {r['ms_per_step']:.3f} ms/step", file=sys.stderr)
     if rank == 0:
         scene = out.pop("_scene", None)
+        dumped = out.pop("_dump", None)
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         out["rccl_ranks"] = rccl_ranks
         out["backend"] = backend
-        if world == 1 and not args.no_cpu_baseline and scene is not None:
+        if world == 1 and args.full and not args.no_cpu_baseline and scene is not None:
             out["cpu_baseline"] = cpu_baseline(args, *scene)
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         if extra:

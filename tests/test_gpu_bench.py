@@ -11,7 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-FAST = ["--steps", "3", "--warmup", "1", "--sustain-seconds", "0", "--no-extra", "--no-cpu-baseline"]
+FAST = ["--steps", "3", "--warmup", "1", "--sustain-seconds", "0", "--no-extra", "--no-cpu-baseline", "--full"]
 
 
 def _line(cmd, env=None, timeout=900):
@@ -40,6 +40,38 @@ def test_single_gpu_line_has_the_contract_and_the_parity_binding():
     assert 0.3 < ce["renderer_mix"]["frac_of_peak"] < ce["bare_chain"]["frac_of_peak"] < 1.0, ce
     assert 0.5 < ce["frac_of_renderer_mix"] < 1.15 and 0.0 < ce["frac_of_ceiling"] < 1.0, ce
     assert out["roofline"]["traffic"] is not None
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract's keys, exactly K timed steps, none of the extras;
+    --dump-outputs writes the last timed step's image, and the same arguments give the same image on a second run."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    outs = [_line([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)]) for d in dirs]
+    for out in outs:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 4 and out["warmup"] == 1 and out["dtype"] == "f16" and out["ms_per_step"] > 0
+        assert abs(out["value"] - 450 * 450 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        for k in ("sustained", "cpu_baseline", "other_workloads", "parity_check", "f16_range"):
+            assert k not in out, k
+        assert "power_ceiling" not in out["roofline"]
+    a, b = [np.load(str(d / "rgb_head.npy")) for d in dirs]
+    assert a.dtype == np.float32 and a.shape == (450 * 450, 3) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+    assert sorted(os.listdir(str(dirs[0]))) == ["rgb_head.npy"]
+
+
+def test_training_step_dumps_its_outputs(tmp_path):
+    import numpy as np
+    out = _line([sys.executable, BENCH, "--workload", "c4", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                env={"DFN_BENCH_PRINT_LOSS": "1"})
+    assert out["steps"] == 5 and "other_workloads" not in out and "sustained" not in out
+    d = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("loss", "loss_head", "loss_com", "rgb_head", "rgb_com", "decoder_params")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+    assert d["rgb_head"].shape == (2048, 3) and d["rgb_com"].shape == (2048, 3) and d["decoder_params"].size == 955242
+    assert abs(float(d["loss"]) - out["last_loss"]) <= 1e-6 * abs(out["last_loss"])
+    assert abs(float(d["loss"]) - float(d["loss_head"]) - float(d["loss_com"])) < 1e-6
 
 
 @pytest.mark.parametrize("workload", ["c2", "c5", "c4"])
@@ -97,7 +129,7 @@ def test_inference_in_the_multi_rank_schedule_over_rccl(workload):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         os.environ.pop(k, None)
     out = _line([sys.executable, BENCH, "--workload", workload, "--steps", "6", "--warmup", "2", "--sustain-seconds", "0",
-                 "--no-extra", "--no-cpu-baseline"], env={"DFN_BENCH_RCCL_WORLD1": "1"})
+                 "--no-extra", "--no-cpu-baseline", "--full"], env={"DFN_BENCH_RCCL_WORLD1": "1"})
     assert out["backend"].startswith("nccl") and out["n_gpus"] == 1 and out["rccl_ranks"] == 1
     assert out["gather"]["async"] and out["gather"]["collective"] == "all_gather_into_tensor" and out["gather"]["ms_alone"] > 0
     assert out["gather"]["render_streams"] == 2
@@ -120,7 +152,7 @@ def test_workload_all_two_ranks_and_fail_fast_without_devices():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         os.environ.pop(k, None)
     out = _line([sys.executable, BENCH, "--gpus", "2", "--workload", "all", "--steps", "2", "--warmup", "1",
-                 "--sustain-seconds", "0", "--no-cpu-baseline"], env={"DFN_BENCH_ONE_GPU": "1"}, timeout=1500)
+                 "--sustain-seconds", "0", "--no-cpu-baseline", "--full"], env={"DFN_BENCH_ONE_GPU": "1"}, timeout=1500)
     assert out["n_gpus"] == 2 and out["config"]["fields"] == 1 and out["gather_check"].get("identical") is True
     ow = out["other_workloads"]
     assert set(ow) == {"c3", "c5", "c4", "c4s"}, sorted(ow)
@@ -143,7 +175,7 @@ def test_workload_all_eight_ranks_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         os.environ.pop(k, None)
     out = _line([sys.executable, BENCH, "--gpus", "8", "--workload", "all", "--steps", "2", "--warmup", "1",
-                 "--sustain-seconds", "0", "--no-cpu-baseline"], env={"DFN_BENCH_ONE_GPU": "1", "OMP_NUM_THREADS": "4"},
+                 "--sustain-seconds", "0", "--no-cpu-baseline", "--full"], env={"DFN_BENCH_ONE_GPU": "1", "OMP_NUM_THREADS": "4"},
                 timeout=2400)
     assert out["n_gpus"] == 8 and out["rccl_ranks"] == 8 and out["backend"] == "gloo"
     assert out["gather_check"].get("identical") is True, out["gather_check"]

@@ -569,3 +569,39 @@ def test_bench_union_of_launch_intervals():
     # two alternating streams, 8 launches of 66 ms that start every 33 ms: 33 ms per launch plus the last one's tail
     iv = [(33.0 * i, 33.0 * i + 66.0) for i in range(8)]
     assert abs(u(iv) / len(iv) - (33.0 * 7 + 66.0) / 8) < 1e-9
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_defaults_and_full():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only; --full brings back the sustained run, the
+    CPU baseline, the other workloads and the checks (each still switched off by its own --no-* option)."""
+    bench = _bench_module()
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.sustain_seconds == 0.0 and a.dump_outputs is None
+    f = bench.parse(["--full"])
+    assert f.full and f.sustain_seconds == 10.0
+    assert bench.parse(["--full", "--sustain-seconds", "0"]).sustain_seconds == 0.0
+    assert bench.parse(["--dump-outputs", "x"]).dump_outputs == "x"
+
+
+def test_bench_write_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; past the size limit a fixed, seeded sample of rows, the same on every run."""
+    bench = _bench_module()
+    img = np.arange(3000, dtype=np.float64).reshape(1000, 3)
+    bench.write_outputs(str(tmp_path / "a"), {"rgb_head": img, "loss": np.float64(0.5)})
+    got = np.load(str(tmp_path / "a" / "rgb_head.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    assert np.load(str(tmp_path / "a" / "loss.npy")) == np.float32(0.5)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 6000)
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), {"rgb_head": img})
+    b, c = [np.load(str(tmp_path / d / "rgb_head.npy")) for d in ("b", "c")]
+    assert b.nbytes <= 6000 and b.shape[1] == 3 and np.array_equal(b, c)
+    assert all(any(np.array_equal(r, s) for s in img.astype(np.float32)) for r in b)
