@@ -33,8 +33,12 @@ int hip_fail(hipError_t e, const char* what) {
     return fail(DFN_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-bool tier_ok(int tier) { return tier == DFN_TIER_F32 || tier == DFN_TIER_BF16 || tier == DFN_TIER_F16; }
-// the training entry points: the f16 tier is inference only (gradients underflow its 5-bit exponent)
+bool tier_ok(int tier) {
+    return tier == DFN_TIER_F32 || tier == DFN_TIER_BF16 || tier == DFN_TIER_F16 || tier == DFN_TIER_F16X3;
+}
+constexpr int N_TIERS = 4;          // size of the tier-indexed tables
+static_assert(DFN_TIER_F16X3 == TIER_F16X3 && DFN_TIER_F16X3 + 1 == N_TIERS, "tier ids");
+// the training entry points: the f16 and f16x3 tiers are inference only (gradients underflow f16's 5-bit exponent)
 bool train_tier_ok(int tier) { return tier == DFN_TIER_F32 || tier == DFN_TIER_BF16; }
 bool field_ok(int field) { return field >= 0 && field <= 2; }
 int prog_field(int field) { return field == DFN_FIELD_TORSO ? FIELD_TORSO : FIELD_HEAD; }
@@ -51,7 +55,7 @@ struct PlanEntry {
     int32_t* dev = nullptr;
 };
 std::mutex g_plan_mu;
-PlanEntry g_plans[3][3];
+PlanEntry g_plans[N_TIERS][3];     // [tier][field]
 
 PlanEntry& plan_of(int tier, int field) {
     std::lock_guard<std::mutex> lk(g_plan_mu);
@@ -208,9 +212,9 @@ extern "C" {
 
 const char* dfn_last_error(void) { return g_err.c_str(); }
 #ifdef DFN_DEV_BUILD      // (dfn_devguard.h: a library built with developer switches says so, and dfanerf._lib refuses it in-tree)
-const char* dfn_version(void) { return "dfanerf 0.2 gfx950 DEV"; }
+const char* dfn_version(void) { return "dfanerf 0.3 gfx950 DEV"; }
 #else
-const char* dfn_version(void) { return "dfanerf 0.2 gfx950"; }
+const char* dfn_version(void) { return "dfanerf 0.3 gfx950"; }
 #endif
 
 long dfn_packed_bytes(int tier, int field) {

@@ -23,17 +23,26 @@
 namespace dfn {
 
 // ---- precision tiers ---------------------------------------------------------------------------
-enum Tier : int { TIER_F32 = 0, TIER_BF16 = 1, TIER_F16 = 2 };
+enum Tier : int { TIER_F32 = 0, TIER_BF16 = 1, TIER_F16 = 2, TIER_F16X3 = 3 };
 // k-slots per half-wave per k-unit: one k-unit = what one 16-byte A-fragment read feeds.
 //   bf16: 8 bf16 per lane  = one v_mfma_f32_32x32x16_bf16  (K=16)
 //   f16 : 8 f16 per lane   = one v_mfma_f32_32x32x16_f16   (K=16; same rate and fragment map as bf16, 10 mantissa
 //                            bits instead of 7: the throughput tier whose rendered RGB stays within the accuracy clause;
 //                            inference only - gradients would underflow f16's 5-bit exponent)
 //   f32 : 4 f32 per lane   = four v_mfma_f32_32x32x2_f32   (K=2 each)
-DFN_HD constexpr bool tier_is16(int tier) { return tier != TIER_F32; }
-DFN_HD int tier_E(int tier) { return tier_is16(tier) ? 8 : 4; }
-DFN_HD int tier_UPT(int tier) { return tier_is16(tier) ? 2 : 4; }        // k-units per 32-feature tile
-DFN_HD int tier_elem_bytes(int tier) { return tier_is16(tier) ? 2 : 4; }
+//   f16x3: the f16 fragment map with split operands: x ~ hi + 2^-11 lo', hi = f16(x), lo' = f16((x - hi) 2^11); a k-unit is a
+//          hi fragment followed by a lo' fragment, and three v_mfma_f32_32x32x16_f16 (hi.hi, hi.lo', lo'.hi; lo'.lo' dropped):
+//          ~22-bit products, f32 accumulation.  16-bit in its fragment map (tier_frag16), f32 in everything else (tier_is16 is
+//          false: positional encoding, epilogue arithmetic, one wave per SIMD like the f32 tier).  Inference only.
+DFN_HD constexpr bool tier_is16(int tier) { return tier == TIER_BF16 || tier == TIER_F16; }     // 16-bit operand arithmetic
+DFN_HD constexpr bool tier_frag16(int tier) { return tier != TIER_F32; }                       // 16-bit fragment map (E = 8)
+DFN_HD constexpr int tier_split(int tier) { return tier == TIER_F16X3 ? 2 : 1; }                // fragments per k-unit and tile
+DFN_HD int tier_E(int tier) { return tier_frag16(tier) ? 8 : 4; }
+DFN_HD int tier_UPT(int tier) { return tier_frag16(tier) ? 2 : 4; }        // k-units per 32-feature tile
+DFN_HD int tier_elem_bytes(int tier) { return tier_frag16(tier) ? 2 : 4; }
+// the split of the f16x3 tier: lo' carries the residual scaled by 2^11 (a normal f16 where the residual itself would be
+// subnormal); a product term with one lo' factor is folded back with SPLIT_INV
+constexpr float SPLIT_SCALE = 2048.0f, SPLIT_INV = 1.0f / 2048.0f;
 
 constexpr int FRAG_BYTES = 1024;            // one A fragment: 64 lanes x 16 B, lane-linear
 constexpr int SLAB_FRAGS = 32;              // ring slot = 32 fragments = 32 KiB

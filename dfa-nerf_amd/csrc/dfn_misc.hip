@@ -21,7 +21,11 @@ __device__ __forceinline__ void pack_body(const int* __restrict__ plan, const fl
     const float v = src >= 0 ? params[src] : 0.f;
     if (tier == TIER_BF16) ((__bf16*)out)[i] = (__bf16)v;       // round-to-nearest-even
     else if (tier == TIER_F16) ((_Float16*)out)[i] = (_Float16)v;
-    else ((float*)out)[i] = v;
+    else if (tier == TIER_F16X3) {
+        // the plan repeats every f16 fragment (512 elements): the even copy holds hi = f16(w), the odd one lo' = f16((w - hi) 2^11)
+        const _Float16 hi = (_Float16)v;
+        ((_Float16*)out)[i] = ((i >> 9) & 1) ? (_Float16)((v - (float)hi) * SPLIT_SCALE) : hi;
+    } else ((float*)out)[i] = v;
 }
 __global__ void pack_kernel(const int* __restrict__ plan, const float* __restrict__ params, void* out, long n,
                             int tier) {

@@ -52,6 +52,11 @@ template <> struct TierCfg<TIER_F16> : TierCfg<TIER_BF16> {};
 template <> struct TierCfg<TIER_F32> {
     static constexpr int E = 4, UPT = 4, WAVES = 4, THREADS = 256, LOADS_PER_SLAB = 8;
 };
+// f16x3: the f16 fragment map, the f32 tier's workgroup (one wave per SIMD: the split B operand of an 8-tile vector is 128
+// registers, like Vec<TIER_F32, 8>, and every tile group carries a second accumulator set)
+template <> struct TierCfg<TIER_F16X3> {
+    static constexpr int E = 8, UPT = 2, WAVES = 4, THREADS = 256, LOADS_PER_SLAB = 8;
+};
 
 constexpr int RING_SLOTS = 3;
 constexpr int RING_BYTES = RING_SLOTS * SLAB_BYTES;
@@ -73,6 +78,17 @@ template <int NT> struct Vec<TIER_F32, NT> {
     float v[16 * NT];
     DFN_DEV void set(int L, float x) { v[L] = x; }
     DFN_DEV float get(int L) const { return v[L]; }
+};
+// split operand (dfn_layout.h, TIER_F16X3): u = hi = f16(x), l = lo' = f16((x - hi) 2^11), both in the f16 tier's slot map
+template <int NT> struct Vec<TIER_F16X3, NT> {
+    f16x8 u[2 * NT];
+    f16x8 l[2 * NT];
+    DFN_DEV void set(int L, float x) {
+        const _Float16 hi = (_Float16)x;
+        u[L >> 3][L & 7] = hi;
+        l[L >> 3][L & 7] = (_Float16)((x - (float)hi) * SPLIT_SCALE);
+    }
+    DFN_DEV float get(int L) const { return (float)u[L >> 3][L & 7] + (float)l[L >> 3][L & 7] * SPLIT_INV; }
 };
 
 // ---- weight stream -------------------------------------------------------------------------------------
@@ -545,6 +561,10 @@ template <int TIER, class CT> constexpr bool use_asm_fetch() { return tier_is16(
 #ifndef DFN_F32_PIN_FRAGS
 #define DFN_F32_PIN_FRAGS 1
 #endif
+// the same pin in the f16x3 tier's gemm_group (one sched_barrier per (hi, lo') fragment pair and its three MFMAs); 0 = none
+#ifndef DFN_X3_PIN_FRAGS
+#define DFN_X3_PIN_FRAGS 1
+#endif
 #ifndef DFN_F32_ASM_DMA
 #define DFN_F32_ASM_DMA 1
 #endif
@@ -630,58 +650,101 @@ template <int TIER> struct Fetch {
 // One tile-group: acc[g] (g < G output tiles) += W x b over k-units [0, KU) of b.
 // Fragments are consumed in stream order [ku][g]; `f` is the running fragment index of the pass.
 // TAIL: number of fragments that follow this group in the pass (-1 = plenty): no prefetch past the end.
+// f16x3 tier: fragments [ku][g][hi, lo'], three MFMAs per (ku, g): acc += hi.hi, accx += hi.lo' + lo'.hi; accx (the terms
+// scaled by 2^11) is folded into acc at the end of the group - every caller reads acc only after gemm_group returns.
 template <int TIER, int G, int KU, int NTB, int TAIL = -1, class CT, class H = NoHook, class SD = NoSide>
 DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch<TIER>& fe, Stream& s,
                         const CT& c, H&& hook = H{}, SD&& side = SD{}) {
+    if constexpr (TIER == TIER_F16X3) {
+        // (the register ring is PF_DEPTH fragments = two (hi, lo') pairs ahead; a depth of 8 parks 6-14 more VGPRs in AGPRs)
+        constexpr int D = PF_DEPTH;
+        f32x16 accx[G];
 #pragma unroll
-    for (int ku = 0; ku < KU; ++ku) {
+        for (int g = 0; g < G; ++g)
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int left = (KU - ku) * G - g - 1;           // fragments after this one in the group
-            constexpr bool ASM = use_asm_fetch<TIER, CT>();
-            if constexpr (ASM) {
-                const int after = (TAIL < 0) ? PF_DEPTH : left + TAIL;             // ... in the pass
-                frag_wait(fe.buf[f % PF_DEPTH], after < PF_DEPTH - 1 ? after : PF_DEPTH - 1);     // fragment f has landed
-            }
-            const u32x4 a = fe.buf[f % PF_DEPTH];
-            if constexpr (!ASM) {
-                if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook);
-            }
-            if constexpr (TIER == TIER_BF16) {
-                acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), b.u[ku],
-                                                                 acc[g], 0, 0, 0);
-            } else if constexpr (TIER == TIER_F16) {
-                acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), b.u[ku],
-                                                                acc[g], 0, 0, 0);
-            } else {
-                const f32x4 af = __builtin_bit_cast(f32x4, a);
+            for (int r = 0; r < 16; ++r) accx[g][r] = 0.f;
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], b.v[4 * ku + e], acc[g], 0, 0, 0);
-            }
-            if constexpr (ASM) {      // refill the slot just consumed (the MFMA has read its operands when it issued)
-                if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook);
-            }
+        for (int ku = 0; ku < KU; ++ku) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int left = ((KU - ku) * G - g) * 2 - 1;     // fragments after the hi one in the group
+                const u32x4 ah = fe.buf[f % D];
+                if (TAIL < 0 || left + TAIL >= D) fe.load(f % D, f + D, s, c, hook);
+                ++f;
+                const u32x4 al = fe.buf[f % D];
+                if (TAIL < 0 || left - 1 + TAIL >= D) fe.load(f % D, f + D, s, c, hook);
+                ++f;
+                const f16x8 wh = __builtin_bit_cast(f16x8, ah), wl = __builtin_bit_cast(f16x8, al);
+                acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, b.u[ku], acc[g], 0, 0, 0);
+                accx[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, b.l[ku], accx[g], 0, 0, 0);
+                accx[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, b.u[ku], accx[g], 0, 0, 0);
 #ifdef DFN_GEMM_SCHEDBAR
-            // compiler-scheduled fragment reads: pin every (read of fragment f + PF_DEPTH, MFMA of fragment f) pair where the
-            // source puts it.  Left alone, the machine scheduler sinks each ds_read_b128 next to the MFMA that consumes it
-            // (fewer live registers) and the LDS latency of every fragment is exposed: s_waitcnt lgkmcnt(0/1) in front of
-            // every MFMA, matrix pipe 35 % busy in the dX kernels
-            if constexpr (!ASM) __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
+                __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
 #else
-            // f32 tier, kernels that do not record (inference, dX chain): the same pin (round 6, -DDFN_GEMM_SCHEDBAR=0 builds:
-            // c2_f32 317.8 -> 314.7 ms, dX 1230 -> 1216 us per field; the recording forward LOSES 20 us with it and stays free;
-            // profiles/r06za_*)
-            if constexpr (!ASM && TIER == TIER_F32 && !CT::rec_on && (DFN_F32_PIN_FRAGS != 0)) __builtin_amdgcn_sched_barrier(0);
+                // the f32 tier's pin: each (reads of fragments f + D, MFMAs of the pair f) group stays where the source puts it
+                if constexpr (!CT::rec_on && (DFN_X3_PIN_FRAGS != 0)) __builtin_amdgcn_sched_barrier(0);
 #endif
-            ++f;
-        }
-        side(ku);
+            }
+            side(ku);
 #ifdef DFN_PIPE_SCHEDBAR
-        // pin the side work of a k-step between its MFMAs and the next step's: without it the scheduler pulls the
-        // convert / ReLU units together right behind the last MFMA of their accumulators (where they wait for it)
-        if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
 #endif
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[g][r] = __builtin_fmaf(accx[g][r], SPLIT_INV, acc[g][r]);
+    } else {
+#pragma unroll
+        for (int ku = 0; ku < KU; ++ku) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int left = (KU - ku) * G - g - 1;           // fragments after this one in the group
+                constexpr bool ASM = use_asm_fetch<TIER, CT>();
+                if constexpr (ASM) {
+                    const int after = (TAIL < 0) ? PF_DEPTH : left + TAIL;             // ... in the pass
+                    frag_wait(fe.buf[f % PF_DEPTH], after < PF_DEPTH - 1 ? after : PF_DEPTH - 1);     // fragment f has landed
+                }
+                const u32x4 a = fe.buf[f % PF_DEPTH];
+                if constexpr (!ASM) {
+                    if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook);
+                }
+                if constexpr (TIER == TIER_BF16) {
+                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), b.u[ku],
+                                                                     acc[g], 0, 0, 0);
+                } else if constexpr (TIER == TIER_F16) {
+                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), b.u[ku],
+                                                                    acc[g], 0, 0, 0);
+                } else {
+                    const f32x4 af = __builtin_bit_cast(f32x4, a);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], b.v[4 * ku + e], acc[g], 0, 0, 0);
+                }
+                if constexpr (ASM) {      // refill the slot just consumed (the MFMA has read its operands when it issued)
+                    if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook);
+                }
+#ifdef DFN_GEMM_SCHEDBAR
+                // compiler-scheduled fragment reads: pin every (read of fragment f + PF_DEPTH, MFMA of fragment f) pair where the
+                // source puts it.  Left alone, the machine scheduler sinks each ds_read_b128 next to the MFMA that consumes it
+                // (fewer live registers) and the LDS latency of every fragment is exposed: s_waitcnt lgkmcnt(0/1) in front of
+                // every MFMA, matrix pipe 35 % busy in the dX kernels
+                if constexpr (!ASM) __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
+#else
+                // f32 tier, kernels that do not record (inference, dX chain): the same pin (round 6, -DDFN_GEMM_SCHEDBAR=0 builds:
+                // c2_f32 317.8 -> 314.7 ms, dX 1230 -> 1216 us per field; the recording forward LOSES 20 us with it and stays free;
+                // profiles/r06za_*)
+                if constexpr (!ASM && TIER == TIER_F32 && !CT::rec_on && (DFN_F32_PIN_FRAGS != 0)) __builtin_amdgcn_sched_barrier(0);
+#endif
+                ++f;
+            }
+            side(ku);
+#ifdef DFN_PIPE_SCHEDBAR
+            // pin the side work of a k-step between its MFMAs and the next step's: without it the scheduler pulls the
+            // convert / ReLU units together right behind the last MFMA of their accumulators (where they wait for it)
+            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
     }
 }
 
@@ -762,6 +825,29 @@ DFN_DEV void acc_to_vec(const f32x16 (&acc)[G], Vec<TIER, NT>& v, int t0) {
                 }
                 const u32x4 q = {w[0], w[1], w[2], w[3]};
                 v.u[2 * (t0 + g) + h] = __builtin_bit_cast(pk8, q);
+            }
+        }
+    } else if constexpr (TIER == TIER_F16X3) {
+        // bias and ReLU in f32 (done: the accumulators started at the bias), then the split per value pair: v_cvt_pk_f16_f32
+        // (hi), back to f32, the residual scaled by 2^11 (both exact in f32), v_cvt_pk_f16_f32 (lo')
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                unsigned wh[4], wl[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    f32x2 x = {acc[g][8 * h + 2 * e], acc[g][8 * h + 2 * e + 1]};
+                    if constexpr (RELU) x = f32x2{relu_(x[0]), relu_(x[1])};
+                    const f16x2 hi = __builtin_convertvector(x, f16x2);
+                    const f32x2 d = (x - __builtin_convertvector(hi, f32x2)) * SPLIT_SCALE;
+                    const f16x2 lo = __builtin_convertvector(d, f16x2);
+                    wh[e] = __builtin_bit_cast(unsigned, hi);
+                    wl[e] = __builtin_bit_cast(unsigned, lo);
+                }
+                const u32x4 qh = {wh[0], wh[1], wh[2], wh[3]}, ql = {wl[0], wl[1], wl[2], wl[3]};
+                v.u[2 * (t0 + g) + h] = __builtin_bit_cast(f16x8, qh);
+                v.l[2 * (t0 + g) + h] = __builtin_bit_cast(f16x8, ql);
             }
         }
     } else {
@@ -1063,8 +1149,8 @@ DFN_DEV void posenc(Vec<TIER, NT>& v, const float (&p)[3], int half) {
         const int a0 = (c0 % 6) % 3, a1 = (c1 % 6) % 3;
         const bool cos0 = (c0 % 6) >= 3, cos1 = (c1 % 6) >= 3;
         float val;
-        if constexpr (TIER == TIER_F32) {
-            // argument rounded like the reference: fl32(fl32(2^i*pi) * fl32(p/2)); accurate sin/cos
+        if constexpr (TIER == TIER_F32 || TIER == TIER_F16X3) {
+            // argument rounded like the reference (f16x3: the same value, then split by Vec::set): fl32(fl32(2^i*pi) * fl32(p/2)); accurate sin/cos
             const float x = half ? __fmul_rn(PE_FREQ[o1], ph[a1]) : __fmul_rn(PE_FREQ[o0], ph[a0]);
             if (cos0 == cos1) {
                 val = cos0 ? cosf(x) : sinf(x);
@@ -1094,18 +1180,19 @@ DFN_DEV void posenc(Vec<TIER, NT>& v, const float (&p)[3], int half) {
 template <int TIER> struct Prog {
     static constexpr int UPT = TierCfg<TIER>::UPT;
     static constexpr int KU_PE = 2 * UPT, KU_VIEW = UPT, KU_ACT = 8 * UPT, KU_D = 2 * UPT, KU_PD = 4 * UPT;
-    static constexpr int F_LAYER = 8 * KU_ACT;          // fragments of one 256x256 layer (multiple of 32)
-    static constexpr int F_TAIL = 9 * (KU_ACT + KU_VIEW) + KU_ACT;
+    static constexpr int FS = tier_split(TIER);         // fragments per (k-unit, tile): 2 in the f16x3 tier (hi, lo')
+    static constexpr int F_LAYER = 8 * KU_ACT * FS;     // fragments of one 256x256 layer (multiple of 32)
+    static constexpr int F_TAIL = (9 * (KU_ACT + KU_VIEW) + KU_ACT) * FS;
     // head
-    static constexpr int H_FRAGS = 8 * KU_PE + 7 * F_LAYER + 8 * KU_PE + F_TAIL;
+    static constexpr int H_FRAGS = 8 * KU_PE * FS + 7 * F_LAYER + 8 * KU_PE * FS + F_TAIL;
     static constexpr int H_SLABS = (H_FRAGS + SLAB_FRAGS - 1) / SLAB_FRAGS;
     // head bias blob (floats): in(256) L1..L4(4x256) skip(256) L5..L7(3x256) view(288) out(32)
     static constexpr int H_B_IN = 0, H_B_L1 = 256, H_B_SKIP = 5 * 256, H_B_L5 = 6 * 256, H_B_VIEW = 9 * 256,
                          H_B_OUT = 9 * 256 + 288, H_NBIAS = 9 * 256 + 288 + 32;
     // torso
-    static constexpr int F_D = 2 * KU_D;                // fragments of one 64x64 layer
-    static constexpr int T_F_DEFORM = 4 * KU_PE + 10 * F_D + 2 * KU_PE;   // E0 S0 | 10 64x64 layers | ESKIP
-    static constexpr int T_FRAGS = T_F_DEFORM + 8 * KU_PD + 7 * F_LAYER + 8 * KU_PD + F_TAIL;
+    static constexpr int F_D = 2 * KU_D * FS;           // fragments of one 64x64 layer
+    static constexpr int T_F_DEFORM = 4 * KU_PE * FS + 10 * F_D + 2 * KU_PE * FS;   // E0 S0 | 10 64x64 layers | ESKIP
+    static constexpr int T_FRAGS = T_F_DEFORM + 8 * KU_PD * FS + 7 * F_LAYER + 8 * KU_PD * FS + F_TAIL;
     static constexpr int T_SLABS = (T_FRAGS + SLAB_FRAGS - 1) / SLAB_FRAGS;
     // torso bias blob: E0 S0 E1 S1 E2 S2 E3 ESKIP S3 SSKIP E4 S4 EO SO (14 x 64), then the trunk like head
     static constexpr int T_B_E0 = 0, T_B_S0 = 64, T_B_E1 = 128, T_B_S1 = 192, T_B_E2 = 256, T_B_S2 = 320,
@@ -1304,6 +1391,8 @@ DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32
         acc_init<2>(acc, bias + P::T_B_EO, c.half);
         gemm_group<TIER, 2, P::KU_D, 2>(acc, ve, f, fe, s, c);
 #pragma unroll
+        // (f16x3: pe.get is hi + 2^-11 lo', the f32 encoding to ~2^-22 relative - not the exact value the f32 tier adds;
+        // tests/test_f16x3_host.py models it)
         for (int L = 0; L < 32; ++L) pd.set(L, acc[L >> 4][L & 15] + pe.get(L));
         acc_init<2>(acc, bias + P::T_B_SO, c.half);
         gemm_group<TIER, 2, P::KU_D, 2>(acc, vs, f, fe, s, c);

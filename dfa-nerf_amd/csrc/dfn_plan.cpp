@@ -29,27 +29,29 @@ struct Builder {
     long frags = 0;
 
     // one tile group of G output tiles starting at output row row0, over KU k-units of one input vector
+    // (f16x3 tier: every fragment twice in a row - hi, then lo'; the pack kernel tells them apart by the fragment's parity)
     void emit_group(int G, int row0, int KU, const RowFn& rows, const ColFn& cols) {
         const int E = tier_E(tier);
         for (int ku = 0; ku < KU; ++ku)
-            for (int g = 0; g < G; ++g) {
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int i = lane & 31, h = lane >> 5;
-                    const Src src = rows(row0 + 32 * g + i);
-                    for (int e = 0; e < E; ++e) {
-                        const int slot = kslot_to_slot(tier, ku, h, e);
-                        const int col = cols(slot);
-                        int32_t v = -1;
-                        if (src.pid >= 0 && col >= 0) {
-                            const ParamShape sh = param_shape(src.pid);
-                            if (src.row < sh.rows && col < sh.cols)
-                                v = param_offset(src.pid) + src.row * sh.cols + col;
+            for (int g = 0; g < G; ++g)
+                for (int part = 0; part < tier_split(tier); ++part) {
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int i = lane & 31, h = lane >> 5;
+                        const Src src = rows(row0 + 32 * g + i);
+                        for (int e = 0; e < E; ++e) {
+                            const int slot = kslot_to_slot(tier, ku, h, e);
+                            const int col = cols(slot);
+                            int32_t v = -1;
+                            if (src.pid >= 0 && col >= 0) {
+                                const ParamShape sh = param_shape(src.pid);
+                                if (src.row < sh.rows && col < sh.cols)
+                                    v = param_offset(src.pid) + src.row * sh.cols + col;
+                            }
+                            plan.push_back(v);
                         }
-                        plan.push_back(v);
                     }
+                    ++frags;
                 }
-                ++frags;
-            }
     }
     // transposed group (backward streams): G tiles of forward-INPUT slots starting at slot0, contraction over the
     // forward-OUTPUT rows carried as KU k-units of a gradient vector

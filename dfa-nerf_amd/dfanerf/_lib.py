@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DFN_LIB: developer override (A/B builds of the kernels); the shipped path is the in-tree library
 LIB_PATH = os.environ.get("DFN_LIB") or os.path.join(_HERE, "libdfanerf.so")
 
-TIER_F32, TIER_BF16, TIER_F16 = 0, 1, 2
+TIER_F32, TIER_BF16, TIER_F16, TIER_F16X3 = 0, 1, 2, 3
 TRAIN_ACT_E4M3 = 0x100      # or'ed into the tier of dfn_train_fwd*: e4m3 instead of e2m1 activations (include/dfanerf.h)
 ACT_E4M3, ACT_E2M1 = 0, 1
 FIELD_HEAD, FIELD_TORSO, FIELD_LISTENER = 0, 1, 2

@@ -9,12 +9,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (DECODER_UNUSED_PREFIXES, DfnFrame, FIELD_HEAD, FIELD_LISTENER, FIELD_TORSO, N_DECODER_PARAMS, TIER_BF16, TIER_F16, TIER_F32,
-                   check, lib)
+from ._lib import (DECODER_UNUSED_PREFIXES, DfnFrame, FIELD_HEAD, FIELD_LISTENER, FIELD_TORSO, N_DECODER_PARAMS, TIER_BF16, TIER_F16, TIER_F16X3,
+                   TIER_F32, check, lib)
 
-# "f16": v_mfma_f32_32x32x16_f16, the throughput tier (inference only); "bf16": also the 16-bit training tier
-TIERS = {"f32": TIER_F32, "bf16": TIER_BF16, "f16": TIER_F16, TIER_F32: TIER_F32, TIER_BF16: TIER_BF16,
-         TIER_F16: TIER_F16}
+# "f16": v_mfma_f32_32x32x16_f16, the throughput tier (inference only); "bf16": also the 16-bit training tier;
+# "f16x3": split f16 operands (hi + 2^-11 lo', three f16 MFMAs per product), the f32 tier's accuracy in f16's range (inference only)
+TIERS = {"f32": TIER_F32, "bf16": TIER_BF16, "f16": TIER_F16, "f16x3": TIER_F16X3, TIER_F32: TIER_F32, TIER_BF16: TIER_BF16,
+         TIER_F16: TIER_F16, TIER_F16X3: TIER_F16X3}
+# tiers whose operands are f16 values (hi and lo' alike): f16's range, guarded by f16guard.check
+F16_RANGE_TIERS = (TIER_F16, TIER_F16X3)
+
+
+def tier_name(tier):
+    """the CLI name of a tier id (or name)"""
+    t = TIERS[tier]
+    return next(k for k, v in TIERS.items() if isinstance(k, str) and v == t)
 
 
 def _stream():
@@ -98,7 +107,7 @@ class PackedDecoder:
         self.flat = flat_params
         self.device = flat_params.device
         self.packed = {}
-        self.f16_bounds = None          # f16 tier: calibrated max |activation| per layer (f16guard.activation_bounds), once known
+        self.f16_bounds = None          # f16 / f16x3 tier: calibrated max |activation| per layer (f16guard.activation_bounds), once known
         self.f16_weight_max = None
         for f in fields:
             nbytes = check(lib.dfn_packed_bytes(self.tier, f), "dfn_packed_bytes")
@@ -106,12 +115,12 @@ class PackedDecoder:
         self.repack()
 
     def repack(self):
-        if self.tier == TIERS["f16"]:
+        if self.tier in F16_RANGE_TIERS:
             # half precision's range (f16guard.py): a weight beyond it would be packed as inf.  One device reduction and one
-            # host read per (re)pack - the f16 tier is inference only: it packs once per checkpoint, not once per step
+            # host read per (re)pack - the f16 tiers are inference only: they pack once per checkpoint, not once per step
             from . import f16guard
             self.f16_weight_max = f16guard.weight_bound(self.flat)
-            f16guard.check(None, self.f16_weight_max, what="a decoder parameter")
+            f16guard.check(None, self.f16_weight_max, what="a decoder parameter", tier=tier_name(self.tier))
         for f, buf in self.packed.items():
             check(lib.dfn_pack_weights(self.tier, f, _ptr(self.flat), _ptr(buf), _stream()), "dfn_pack_weights")
 

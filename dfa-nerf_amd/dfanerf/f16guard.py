@@ -185,8 +185,10 @@ def activation_bounds(flat_params, frames, sig_heads, sig_torsos, z_shape, z_app
     return out
 
 
-def check(bounds, weight_max=None, margin=MARGIN, what="the decoder"):
-    """raise F16RangeError if a calibrated bound x margin does not fit f16; -> the largest activation bound otherwise"""
+def check(bounds, weight_max=None, margin=MARGIN, what="the decoder", tier="f16"):
+    """raise F16RangeError if a calibrated bound x margin does not fit f16; -> the largest activation bound otherwise.
+    tier: the tier being guarded - "f16", or "f16x3" (split f16 operands: the same range, no accuracy guard; its way out is
+    the f32 tier)"""
     bad, top = [], 0.0
     if weight_max is not None and not (weight_max * margin < F16_MAX):
         bad.append(f"max |parameter| = {weight_max:.4g}")
@@ -195,6 +197,11 @@ def check(bounds, weight_max=None, margin=MARGIN, what="the decoder"):
             top = max(top, v)
             if not (v * margin < F16_MAX):
                 bad.append(f"{field} field, {layer}: max |activation| = {v:.4g}")
+    if bad and tier == "f16x3":
+        raise F16RangeError(
+            f"--hip_tier f16x3: {what} does not fit half precision's range (largest value {F16_MAX:.0f}, calibration margin "
+            f"x{margin:g}): " + "; ".join(bad) + ".  The f16x3 tier's operands are f16 values and its conversions do not "
+            "saturate - it would render inf / NaN.  Use --hip_tier f32 (exact, f32's range)")
     if bad:
         raise F16RangeError(
             f"--hip_tier f16: {what} does not fit half precision's range (largest value {F16_MAX:.0f}, calibration margin "

@@ -95,7 +95,8 @@ _FLAGS = [
 ]
 # build-side additions (not in the reference): precision tier of the HIP renderer and the hierarchical mode
 # --hip_tier: f32 (exact, the parity tier; default) | f16 (the throughput tier: f16 MFMA operands, PSNR-gated) | bf16
-# (the 16-bit TRAINING tier; also selected for the training step when --hip_tier f16)
+# (the 16-bit TRAINING tier; also selected for the training step when --hip_tier f16) | f16x3 (split f16 operands: the f32
+# tier's accuracy at about a third of its time, range-guarded like f16; trains in f32)
 # --image_ext: file type of the rendered frames (upstream writes .jpg, MAIN:722-732; png = the kernel's uint8 output
 # losslessly, which is what the parity tests read back)
 # --hip_train_act: format of the activations the 16-bit training step records for its weight gradients (fp4 | e4m3)
@@ -105,7 +106,9 @@ _EXTRA_FLAGS = [("hip_tier", str, 'f32'), ("hierarchical", None, None), ("image_
                 ("hip_f16_model_psnr", float, 30.0)]
 _EXTRA_HELP = {
     "hip_tier": "precision tier of the HIP path: f32 (exact MFMA products, the parity tier; default) | f16 (throughput tier "
-                "for rendering: f16 MFMA operands, f32 accumulation) | bf16.  TRAINING with f16 or bf16 runs the 16-bit "
+                "for rendering: f16 MFMA operands, f32 accumulation) | f16x3 (rendering with the f32 tier's accuracy at about 3x "
+                "its speed: every operand split into two f16 values, three f16 MFMAs per product; f16's range - a checkpoint "
+                "outside it is refused, dfanerf/f16guard.py; trains in f32) | bf16.  TRAINING with f16 or bf16 runs the 16-bit "
                 "training tier: bf16 MFMA operands in the forward and the dX chain, and the arrays recorded for the backward "
                 "in MX block formats (one power-of-two scale per 64 features x 32 points): the pre-activation gradients as "
                 "MX-fp8 (e4m3; values below amax * 2^-17 of a block flush to zero), the layer inputs as MX-fp4 (e2m1: ONE "
@@ -343,6 +346,7 @@ class FrameRenderer:
         self.engine = engine
         self.decoder, self.args = decoder, args
         self.tier = tier or getattr(args, "hip_tier", "f32")
+        self.requested = self.tier
         # auto: f16 where the checkpoint passes both guards of the f16 tier (check_f16), the exact tier otherwise
         self.auto = self.tier == "auto"
         if self.auto:
@@ -356,15 +360,20 @@ class FrameRenderer:
         self.za = z_app[0, 2 * itr_obj:2 * itr_obj + 2].to(dev).float().contiguous()
         self.n_fine = args.N_importance if getattr(args, "hierarchical", False) else 0
 
+    @property
+    def guarded(self):
+        """the tier renders f16 operands (f16, f16x3, or auto): check_f16 belongs in front of its render loops"""
+        return self.auto or self.requested in ("f16", "f16x3")
+
     def check_f16_range(self, poses, pose_body, signals, max_frames=8, n_rays=256):
-        """f16 tier only (no-op otherwise): calibrate the decoder's activation range on up to `max_frames` of the frames about
+        """f16 and f16x3 tiers only (no-op otherwise): calibrate the decoder's activation range on up to `max_frames` of the frames about
         to be rendered - poses[k] (3x4 host), signals(k) -> (sig_head [96], sig_torso [42]) - in the exact tier, and refuse
         (f16guard.F16RangeError) if half precision cannot hold it with margin: the f16 conversions do not saturate, an
         out-of-range checkpoint would render NaN silently.  The bounds stay on the packed decoder (`f16_bounds`)."""
-        if self.tier != "f16" or len(poses) == 0:
+        if self.tier not in ("f16", "f16x3") or len(poses) == 0:
             return None
         from . import f16guard
-        pk = self.decoder.packed("f16")                     # (its weight bound was checked when it was packed)
+        pk = self.decoder.packed(self.tier)                 # (its weight bound was checked when it was packed)
         pick = sorted(set(np.linspace(0, len(poses) - 1, min(max_frames, len(poses))).astype(int).tolist()))
         frs, sh, stt = [], [], []
         for k in pick:
@@ -377,8 +386,8 @@ class FrameRenderer:
         with torch.no_grad():
             pk.f16_bounds = f16guard.activation_bounds(pk.flat, frs, sh, stt, self.zs, self.za, self.bg, n_rays=n_rays,
                                                        n_fine=self.n_fine if self.args.N_samples == 64 else 0, z_dim=pk.z_dim)
-        top = f16guard.check(pk.f16_bounds, pk.f16_weight_max)
-        print(f"[dfanerf] f16 tier: calibrated on {len(pick)} frames x {n_rays} rays in the exact tier: max |activation| "
+        top = f16guard.check(pk.f16_bounds, pk.f16_weight_max, tier=self.tier)
+        print(f"[dfanerf] {self.tier} tier: calibrated on {len(pick)} frames x {n_rays} rays in the exact tier: max |activation| "
               f"{top:.4g}, max |parameter| {pk.f16_weight_max:.4g} (half precision holds {f16guard.F16_MAX:.0f}; margin x{f16guard.MARGIN:g})")
         return pk.f16_bounds
 
@@ -424,21 +433,29 @@ class FrameRenderer:
                         for n, st in pk.f16_accuracy.items()))
         return pk.f16_accuracy
 
-    def check_f16(self, poses, pose_body, signals, targets=None, max_frames=8, n_rays=256):
+    def check_f16(self, poses, pose_body, signals, targets=None, max_frames=8, n_rays=256, fallback=False):
         """Both guards of the f16 tier in front of a render loop (no-op in any other tier): range, then accuracy.  With
-        --hip_tier auto a refusal switches this renderer to the exact tier instead of raising.  -> the tier that will render."""
+        --hip_tier auto a refusal switches this renderer to the exact tier instead of raising.  The f16x3 tier has the range
+        guard only (it keeps the f32 tier's accuracy); fallback=True (the in-training preview) renders in the exact tier with
+        a warning when it refuses instead of raising.  -> the tier that will render."""
         if self.auto:
             self.tier = "f16"          # (every call decides again: the weights may have changed since the last one)
-        if self.tier != "f16":
+        elif self.requested == "f16x3":
+            self.tier = "f16x3"
+        if self.tier not in ("f16", "f16x3"):
             return self.tier
         from . import f16guard
         try:
             self.check_f16_range(poses, pose_body, signals, max_frames, n_rays)
-            self.check_f16_accuracy(poses, pose_body, signals, max_frames, n_rays, targets=targets)
+            if self.tier == "f16":
+                self.check_f16_accuracy(poses, pose_body, signals, max_frames, n_rays, targets=targets)
         except (f16guard.F16RangeError, f16guard.F16AccuracyError) as e:
-            if not self.auto:
+            if self.auto:
+                print(f"[dfanerf] --hip_tier auto: rendering in the exact tier (f32): {e}")
+            elif fallback and self.tier == "f16x3":
+                print(f"[dfanerf] WARNING: --hip_tier f16x3 refused for this preview, rendering it in the exact tier (f32): {e}")
+            else:
                 raise
-            print(f"[dfanerf] --hip_tier auto: rendering in the exact tier (f32): {e}")
             self.tier = "f32"
         return self.tier
 
@@ -809,8 +826,8 @@ def check_supported(args):
         bad.append(f"--n_object {args.n_object}")
     # (--n_object > 1, the flag's default: accepted like upstream - and like upstream the run stops in the setup loop over the
     # persons, train(): the reference builds ONE dataset, `datadir = [args.datadir]` (MAIN:449), and indexes it per person)
-    if args.hip_tier not in ("f32", "f16", "bf16", "auto"):
-        bad.append(f"--hip_tier {args.hip_tier} (f32 | f16 | bf16 | auto)")
+    if args.hip_tier not in ("f32", "f16", "f16x3", "bf16", "auto"):
+        bad.append(f"--hip_tier {args.hip_tier} (f32 | f16 | f16x3 | bf16 | auto)")
     if getattr(args, "hip_train_act", "fp4") not in ("fp4", "e4m3"):
         bad.append(f"--hip_train_act {args.hip_train_act} (fp4 | e4m3)")
     if bad:
@@ -913,7 +930,7 @@ def train():
             pf = engine.FramePrefetcher(enc, renderer.decoder.packed(renderer.tier), renderer.zs, renderer.za,
                                         args.smo_size if smoothed else 0, args.smo_torse_size if smoothed else 0, fields=2,
                                         length=len_sig)
-        if (renderer.tier == "f16" or renderer.auto) and frame_ids:
+        if renderer.guarded and frame_ids:
             # range guard of the f16 tier (f16guard.py): a few hundred rays of up to eight of these frames through the exact
             # tier, with their own poses and signals; refuses a checkpoint whose activations half precision cannot hold
             def sig_of(k):
@@ -983,7 +1000,11 @@ def train():
     from . import training
     # the 16-bit training tier is bf16 (f16, the inference throughput tier, has too little exponent range for gradients)
     tier = getattr(args, "hip_tier", "f32")
-    tier = "f32" if tier == "auto" else tier        # (auto = the fastest tier that keeps the accuracy clause: training is exact)
+    # (auto = the fastest tier that keeps the accuracy clause: training is exact; f16x3 asks for the f32 tier's numbers: so does its
+    # training step)
+    if tier == "f16x3":
+        print("[dfanerf] --hip_tier f16x3: the training step runs in the f32 tier (f16x3 renders only)")
+    tier = "f32" if tier in ("auto", "f16x3") else tier
     train_buf = training.TrainBuffers("bf16" if tier == "f16" else tier, args.N_rand, dev,
                                       n_fine=args.N_importance if getattr(args, "hierarchical", False) else 0,
                                       act_format=getattr(args, "hip_train_act", None), n_coarse=args.N_samples)
@@ -1062,11 +1083,13 @@ def train():
                                               len(i_train) + len(i_val), embed_fn=embed_fn)
                     return sg[0], st_
             test_ids = [i_val[t] for t in range(0, len(i_val), 100)]
-            if (renderer.tier == "f16" or renderer.auto) and test_ids:
+            if renderer.guarded and test_ids:
                 # the weights change every step: both guards of the f16 tier again on the frames about to be rendered, the model's
-                # own PSNR measured against their ground truth (this render used to run unguarded)
+                # own PSNR measured against their ground truth (this render used to run unguarded).  f16x3: a range
+                # refusal renders this preview in f32 with a warning instead of ending the run
                 renderer.check_f16([poses_host[j] for j in test_ids], poses_host[0], lambda k: test_signals(test_ids[k]),
-                                   targets=lambda k: (_imread(ds['imgs'][test_ids[k]]), _imread(ds['imgs_com'][test_ids[k]])))
+                                   targets=lambda k: (_imread(ds['imgs'][test_ids[k]]), _imread(ds['imgs_com'][test_ids[k]])),
+                                   fallback=True)
             for testimg_i in range(0, len(i_val), 100):
                 img_id = i_val[testimg_i]
                 with torch.no_grad():

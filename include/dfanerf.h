@@ -37,6 +37,11 @@ extern "C" {
 #define DFN_TIER_F16 2      /* v_mfma_f32_32x32x16_f16: f16 operands (10 mantissa bits), f32 accumulate; same rate as bf16.
                              * Inference entry points only (pack / fold / render / decoder): the training entry points
                              * return DFN_E_ARG for it (gradients underflow f16's exponent range). */
+#define DFN_TIER_F16X3 3    /* v_mfma_f32_32x32x16_f16 on split operands x ~ hi + 2^-11 lo' (hi = f16(x), lo' = f16((x - hi) 2^11)):
+                             * hi.hi + hi.lo' + lo'.hi, f32 accumulate - ~22-bit products (the f32 tier's accuracy) at 3 f16 MFMAs per
+                             * K = 16 on weights and activations alike (Decoder.forward, DEC:277-349).  The weight stream interleaves a
+                             * hi and a lo' fragment per k-unit: dfn_packed_bytes is twice the f16 tier's.  f16's range (|x| <= 65504).
+                             * Inference entry points only, like DFN_TIER_F16: the training entry points return DFN_E_ARG for it. */
 
 #define DFN_FIELD_HEAD 0        /* DEC:303-305  fc_in / fc_p_skips       */
 #define DFN_FIELD_TORSO 1       /* DEC:297-299, 308-309, 324-325 deform_net + fc_in_torso / fc_p_skips_torso */
@@ -45,7 +50,8 @@ extern "C" {
 #define DFN_N_DECODER_PARAMS 955242
 
 const char* dfn_last_error(void);
-/* library build info: "dfanerf <version> gfx950".  ABI notes - 0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
+/* library build info: "dfanerf <version> gfx950".  ABI notes - 0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
+ * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
  * the workspace's per-slice partials in EVERY tier - dbias is written by dfn_weight_bias_grad_reduce (a caller of _partials alone gets
  * no bias gradient; tests/test_gpu_wgrad.py holds the pair to the one-call form bit for bit). */

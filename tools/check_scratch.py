@@ -6,7 +6,10 @@ on every MLP pass (round 1: the Stream struct indexed by a runtime field bit cos
 traffic per frame).  Reads the kernel metadata hipcc leaves in the device ISA (--save-temps) and fails if any of those
 kernels has a private segment or a `scratch_` instruction in its body.
 
-usage: check_scratch.py <file.s> [...]"""
+--agpr-spill-ok: the kernels run one wave per SIMD with the whole 512-register file (the f16x3 tier): VGPRs the allocator parks
+in accumulator registers (vgpr_spill_count > 0 with no private segment and no scratch instruction) move no memory and pass.
+
+usage: check_scratch.py [--agpr-spill-ok] <file.s> [...]"""
 import re
 import sys
 
@@ -26,6 +29,8 @@ def kernels(text):
 
 
 def main(paths):
+    agpr_ok = "--agpr-spill-ok" in paths
+    paths = [p for p in paths if p != "--agpr-spill-ok"]
     bad = seen = 0
     for p in paths:
         for name, (priv, spill, body) in kernels(open(p).read()).items():
@@ -39,7 +44,7 @@ def main(paths):
                 continue
             seen += 1
             n_scr = len(re.findall(r"^\s+scratch_", body, re.M))
-            ok = priv == 0 and spill == 0 and n_scr == 0
+            ok = priv == 0 and (spill == 0 or agpr_ok) and n_scr == 0
             print(f"{name}: private segment {priv} B, {spill} spilled VGPRs, {n_scr} scratch instructions"
                   + ("" if ok else "   <-- FAIL"))
             bad += not ok
