@@ -27,7 +27,7 @@ mkdir -p "$OBJ"
 # memory) and with the MX-fp8 recorder some bodies exceed LLVM's default budget of 16384 instructions
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-inline-asm -mllvm -pragma-unroll-threshold=200000 -I$SRC -I$HERE/../include $DFN_EXTRA_FLAGS"
 HDR_HASH="$( (cat "$SRC"/*.h "$HERE"/../include/*.h; echo "$FLAGS" | sed "s#$HERE#.#g"; hipcc --version 2>/dev/null | head -2) | sha256sum | cut -d' ' -f1)"
-UNITS="dfn_render dfn_render_f32 dfn_render_bf16 dfn_render_bf16e dfn_render_f16 dfn_render_f16x3 dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
+UNITS="dfn_render dfn_render_f32 dfn_render_bf16 dfn_render_bf16e dfn_render_f16 dfn_render_f16x3 dfn_render_f32_w128 dfn_render_f16_w128 dfn_render_f16x3_w128 dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
 # the library's own stamp (next to the .so: it travels with it to the GPU box, the object directory does not): everything it
 # is made from, hashed - an up-to-date library is not rebuilt
 LIB_HASH="$( (echo "$HDR_HASH"; cat "$SRC"/*.hip "$SRC"/*.cpp) | sha256sum | cut -d' ' -f1)"
@@ -48,13 +48,14 @@ g++ -O2 -std=c++17 -fPIC -I"$SRC" -I"$HERE/../include" -c "$SRC/dfn_plan.cpp" -o
 for p in "${pids[@]}"; do wait $p; done
 # the asm fragment fetch (DFN_ASM_FETCH) is only safe if nothing touches an in-flight destination register
 # (f16x3: compiler-scheduled fragment reads, checked all the same)
-for t in bf16 bf16e f16 f16x3; do
+# (_w128: the 128-wide inference program of the same tier, same rules)
+for t in bf16 bf16e f16 f16x3 f16_w128 f16x3_w128; do
   ISA="$OBJ/dfn_render_$t-hip-amdgcn-amd-amdhsa-gfx950.s"
   if [ -f "$ISA" ]; then
     python3 "$HERE/../tools/check_inflight.py" "$ISA" || { echo "build.sh: in-flight register hazard in the $t render kernels" >&2; exit 1; }
     # ... and the 16-bit inference kernels must not use scratch memory at all (stack objects, spilled VGPRs).  f16x3 runs one
     # wave per SIMD with 512 registers: VGPRs parked in accumulator registers are allowed, memory is not
-    XS=""; [ "$t" = "f16x3" ] && XS="--agpr-spill-ok"
+    XS=""; case "$t" in f16x3*) XS="--agpr-spill-ok";; esac
     python3 "$HERE/../tools/check_scratch.py" $XS "$ISA" || { echo "build.sh: scratch memory in the $t inference kernels" >&2; exit 1; }
   fi
 done

@@ -38,8 +38,29 @@ bool tier_ok(int tier) {
 }
 constexpr int N_TIERS = 4;          // size of the tier-indexed tables
 static_assert(DFN_TIER_F16X3 == TIER_F16X3 && DFN_TIER_F16X3 + 1 == N_TIERS, "tier ids");
+static_assert(DFN_WIDTH_128 == TIER_W128 && (DFN_WIDTH_128 & TIER_MASK) == 0 && DFN_WIDTH_128 != DFN_TRAIN_ACT_E4M3, "flags in the tier argument");
 // the training entry points: the f16 and f16x3 tiers are inference only (gradients underflow f16's 5-bit exponent)
 bool train_tier_ok(int tier) { return tier == DFN_TIER_F32 || tier == DFN_TIER_BF16; }
+// DFN_WIDTH_128 (include/dfanerf.h) rides in the tier argument.  The inference entry points take it off with take_width(): tiers
+// f32 / f16 / f16x3 only (bf16 is the training tier and stays padded).  Every other entry point that takes a tier refuses it
+// with no_width(), before any HIP call.
+bool has_width(int tier) { return tier >= 0 && (tier & DFN_WIDTH_128) != 0; }
+int no_width(int tier, const char* who) {
+    if (!has_width(tier)) return DFN_OK;
+    return fail(DFN_E_ARG, std::string(who) + ": DFN_WIDTH_128 selects the 128-wide INFERENCE program (dfn_packed_bytes, dfn_pack_weights, "
+                           "dfn_pack_plan, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd); training "
+                           "and everything else stay on the padded 256-wide layout");
+}
+int take_width(int& tier, int& width, const char* who) {
+    width = 256;
+    if (!has_width(tier)) return DFN_OK;
+    tier &= ~DFN_WIDTH_128;
+    width = 128;
+    if (tier == DFN_TIER_BF16)
+        return fail(DFN_E_ARG, std::string(who) + ": DFN_WIDTH_128 applies to DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 (bf16 is the "
+                               "training tier and stays padded)");
+    return DFN_OK;
+}
 bool field_ok(int field) { return field >= 0 && field <= 2; }
 int prog_field(int field) { return field == DFN_FIELD_TORSO ? FIELD_TORSO : FIELD_HEAD; }
 // training entry points: head, torso and (round 6) the listener, i.e. the head's program on fc_in_listener / fc_p_skips_listener
@@ -55,12 +76,12 @@ struct PlanEntry {
     int32_t* dev = nullptr;
 };
 std::mutex g_plan_mu;
-PlanEntry g_plans[N_TIERS][3];     // [tier][field]
+PlanEntry g_plans[2][N_TIERS][3];     // [width 256 / 128][tier][field]
 
-PlanEntry& plan_of(int tier, int field) {
+PlanEntry& plan_of(int tier, int field, int width) {
     std::lock_guard<std::mutex> lk(g_plan_mu);
-    PlanEntry& e = g_plans[tier][field];
-    if (e.host.empty()) e.n_frags = build_pack_plan(tier, field, e.host);
+    PlanEntry& e = g_plans[width == 128 ? 1 : 0][tier][field];
+    if (e.host.empty()) e.n_frags = build_pack_plan(tier, field, e.host, width);
     return e;
 }
 
@@ -218,17 +239,19 @@ const char* dfn_version(void) { return "dfanerf 0.3 gfx950"; }
 #endif
 
 long dfn_packed_bytes(int tier, int field) {
+    int width;
+    if (take_width(tier, width, "dfn_packed_bytes") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field)) return fail(DFN_E_ARG, "dfn_packed_bytes: bad tier/field");
     ProgramInfo pi;
-    program_info(tier, prog_field(field), &pi);
+    program_info(tier, prog_field(field), &pi, width);
     return (long)pi.n_slabs * SLAB_BYTES;
 }
 
-long dfn_pack_plan(int tier, int field, int32_t* plan_host, long capacity) {
+static long pack_plan_impl(int tier, int width, int field, int32_t* plan_host, long capacity) {
     if (!tier_ok(tier) || !field_ok(field)) return fail(DFN_E_ARG, "dfn_pack_plan: bad tier/field");
-    PlanEntry& e = plan_of(tier, field);
+    PlanEntry& e = plan_of(tier, field, width);
     ProgramInfo pi;
-    program_info(tier, prog_field(field), &pi);
+    program_info(tier, prog_field(field), &pi, width);
     if (e.n_frags != pi.n_frags)
         return fail(DFN_E_ARG, "dfn_pack_plan: planner and kernel disagree on the fragment count (" +
                                    std::to_string(e.n_frags) + " vs " + std::to_string(pi.n_frags) + ")");
@@ -239,12 +262,17 @@ long dfn_pack_plan(int tier, int field, int32_t* plan_host, long capacity) {
     }
     return n;
 }
+long dfn_pack_plan(int tier, int field, int32_t* plan_host, long capacity) {
+    int width;
+    if (take_width(tier, width, "dfn_pack_plan") != DFN_OK) return DFN_E_ARG;
+    return pack_plan_impl(tier, width, field, plan_host, capacity);
+}
 
-// device copy of the forward pack plan of (tier, field), uploaded on first use
-static int fwd_plan_dev(int tier, int field, const int32_t** dev, long* n_out) {
-    const long n = dfn_pack_plan(tier, field, nullptr, 0);
+// device copy of the forward pack plan of (tier, field, width), uploaded on first use
+static int fwd_plan_dev(int tier, int field, const int32_t** dev, long* n_out, int width = 256) {
+    const long n = pack_plan_impl(tier, width, field, nullptr, 0);
     if (n < 0) return (int)n;
-    PlanEntry& e = plan_of(tier, field);
+    PlanEntry& e = plan_of(tier, field, width);
     std::lock_guard<std::mutex> lk(g_plan_mu);
     if (!e.dev) {
         hipError_t err = hipMalloc((void**)&e.dev, n * sizeof(int32_t));
@@ -258,12 +286,14 @@ static int fwd_plan_dev(int tier, int field, const int32_t** dev, long* n_out) {
 }
 
 int dfn_pack_weights(int tier, int field, const float* params, void* packed, void* stream) {
+    int width;
+    if (take_width(tier, width, "dfn_pack_weights") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field) || !params || !packed)
         return fail(DFN_E_ARG, "dfn_pack_weights: bad argument");
     if (param_offset(P_COUNT) != N_DECODER_PARAMS) return fail(DFN_E_ARG, "internal: parameter table size");
     const int32_t* plan;
     long n;
-    const int rc = fwd_plan_dev(tier, field, &plan, &n);
+    const int rc = fwd_plan_dev(tier, field, &plan, &n, width);
     if (rc != DFN_OK) return rc;
     hipError_t err = launch_pack(plan, params, packed, n, tier, (hipStream_t)stream);
     if (err != hipSuccess) return hip_fail(err, "pack_kernel");
@@ -271,6 +301,8 @@ int dfn_pack_weights(int tier, int field, const float* params, void* packed, voi
 }
 
 long dfn_bias_floats(int tier, int field) {
+    int width;      // (accepted and ignored: the 128-wide program reads the same blob)
+    if (take_width(tier, width, "dfn_bias_floats") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field)) return fail(DFN_E_ARG, "dfn_bias_floats: bad tier/field");
     ProgramInfo pi;
     program_info(tier, prog_field(field), &pi);
@@ -279,6 +311,8 @@ long dfn_bias_floats(int tier, int field) {
 
 int dfn_fold_bias(int tier, int field, const float* params, const float* signal, const float* z_shape,
                   const float* z_app, float* bias, void* stream) {
+    int width;      // (accepted and ignored: the blob keeps its layout, the narrow kernels read the first 128 entries of each vector)
+    if (take_width(tier, width, "dfn_fold_bias") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field) || !params || !z_shape || !z_app || !bias)
         return fail(DFN_E_ARG, "dfn_fold_bias: bad argument");
     if (field != DFN_FIELD_LISTENER && !signal) return fail(DFN_E_ARG, "dfn_fold_bias: signal is NULL");
@@ -290,6 +324,7 @@ int dfn_fold_bias(int tier, int field, const float* params, const float* signal,
 
 int dfn_fold_bias_bwd(int tier, int field, const float* params, const float* signal, const float* z_shape,
                       const float* z_app, const float* dbias, float* grad_flat, float* d_signal, void* stream) {
+    if (no_width(tier, "dfn_fold_bias_bwd") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field) || !params || !z_shape || !z_app || !dbias || !grad_flat)
         return fail(DFN_E_ARG, "dfn_fold_bias_bwd: bad argument");
     if (field != DFN_FIELD_LISTENER && !signal) return fail(DFN_E_ARG, "dfn_fold_bias_bwd: signal is NULL");
@@ -314,6 +349,8 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
                            const float* bias_head, const float* bias_torso, const float* bg_f32,
                            const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
                            float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream) {
+    int width;
+    if (take_width(tier, width, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !frame || !packed_head || !bias_head || !rgb_head)
         return fail(DFN_E_ARG, "dfn_render_fwd: bad argument");
     const DfnFrame& F = *frame;
@@ -331,8 +368,8 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
         return fail(DFN_E_ARG, "dfn_render_fwd: ray range outside the image");
     // the kernel reads [head | torso] biases from one LDS image: they must be adjacent in memory
     ProgramInfo ph, pt;
-    program_info(tier, FIELD_HEAD, &ph);
-    program_info(tier, FIELD_TORSO, &pt);
+    program_info(tier, FIELD_HEAD, &ph, width);
+    program_info(tier, FIELD_TORSO, &pt, width);
     if (F.fields == 2 && bias_torso != bias_head + ph.n_bias)
         return fail(DFN_E_ARG, "dfn_render_fwd: bias_torso must directly follow bias_head in memory");
     RenderArgs A;
@@ -359,7 +396,7 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
     A.act_e4m3 = 0;
     A.loss = DfnTrainLoss{};
     A.clock_probe = g_clock_probe;
-    hipError_t err = launch_render(tier, A, (hipStream_t)stream);
+    hipError_t err = launch_render(tier, A, (hipStream_t)stream, width);
     if (err != hipSuccess) return hip_fail(err, "render_kernel");
     return DFN_OK;
 }
@@ -404,6 +441,7 @@ long dfn_train_rows(int field, int what) {
 }
 
 long dfn_packed_bwd_bytes(int tier, int field) {
+    if (no_width(tier, "dfn_packed_bwd_bytes") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !train_field_ok(field)) return fail(DFN_E_ARG, "dfn_packed_bwd_bytes: bad tier/field");
     ProgramInfo pi;
     bwd_program_info(tier, bwd_field(field), &pi);
@@ -432,6 +470,7 @@ static int bwd_plan_dev(int tier, int field, const int32_t** dev, long* n_out) {
 }
 
 int dfn_pack_weights_bwd(int tier, int field, const float* params, void* packed_T, void* stream) {
+    if (no_width(tier, "dfn_pack_weights_bwd") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !train_field_ok(field) || !params || !packed_T)
         return fail(DFN_E_ARG, "dfn_pack_weights_bwd: bad argument");
     const int32_t* plan;
@@ -446,6 +485,7 @@ int dfn_pack_weights_bwd(int tier, int field, const float* params, void* packed_
 int dfn_train_prepare(int tier, const float* params, const float* signal_head, const float* signal_torso,
                       const float* z_shape, const float* z_app, void* packed_head, void* packed_torso, void* packed_T_head,
                       void* packed_T_torso, float* bias_head, float* bias_torso, void* stream) {
+    if (no_width(tier, "dfn_train_prepare") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !params || !signal_head || !signal_torso || !z_shape || !z_app || !packed_head ||
         !packed_torso || !packed_T_head || !packed_T_torso || !bias_head || !bias_torso)
         return fail(DFN_E_ARG, "dfn_train_prepare: bad argument");
@@ -480,6 +520,7 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
                           bool hier, void* stream, const DfnTrainLoss* loss = nullptr, bool with_loss = false) {
     const char* who = hier ? "dfn_train_fwd_hier" : "dfn_train_fwd";
     // the format flag rides in the tier argument (include/dfanerf.h: DFN_TRAIN_ACT_E4M3); 16-bit tier only
+    if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;
     const int act_e4m3 = (tier & DFN_TRAIN_ACT_E4M3) != 0;
     if (tier >= 0) tier &= ~DFN_TRAIN_ACT_E4M3;
     if (act_e4m3 && tier != DFN_TIER_BF16) return fail(DFN_E_ARG, std::string(who) + ": DFN_TRAIN_ACT_E4M3 applies to DFN_TIER_BF16 only");
@@ -672,6 +713,7 @@ int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, co
 
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,
                 const uint32_t* masks, long NP, void* dy_T, void* stream) {
+    if (no_width(tier, "dfn_mlp_bwd") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !train_field_ok(field) || !packed_T || !samples || !dsamples || !masks || !dy_T ||
         NP <= 0 || NP % 32)
         return fail(DFN_E_ARG, "dfn_mlp_bwd: bad argument");
@@ -713,6 +755,7 @@ static int ensure_eof(WgradEntry& w, int tier, int field) {
 // stages: 1 = the GEMMs (partial sums into the workspace), 2 = the reduction of the slices, 3 = both
 static int weight_grad_impl(int tier, int field, int act_format, const void* dy_T, const void* act_T, long NP, float* workspace,
                             float* grad_flat, float* dbias, void* stream, const char* who, int stages = 3, int which = 3) {
+    if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;
     const bool gemm = stages & 1, red = stages & 2;
     if (which < 1 || which > 3 || (which != 3 && (tier != DFN_TIER_F32 || red)))
         return fail(DFN_E_ARG, std::string(who) + ": `which` selects the f32 tier's two GEMM launches (1: 256 x 256, 2: the others, 3: both)");
@@ -912,6 +955,7 @@ int dfn_weight_bias_grad_reduce(int tier, int field, long NP, float* workspace, 
 }
 
 int dfn_bias_grad(int tier, int field, const void* dy_T, long NP, float* workspace, float* dbias, void* stream) {
+    if (no_width(tier, "dfn_bias_grad") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !train_field_ok(field) || !dy_T || !workspace || !dbias || NP <= 0)
         return fail(DFN_E_ARG, "dfn_bias_grad: bad argument");
     WgradEntry& w = wgrad_of(field);
@@ -947,6 +991,7 @@ int dfn_zero_async(void* p, long bytes, void* stream) {
 
 int dfn_signal_grad(int tier, int field, const float* params, const void* dy_T, long NP, float* workspace, float* d_signal,
                     void* stream) {
+    if (no_width(tier, "dfn_signal_grad") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || (field != 0 && field != 1) || !params || !dy_T || !workspace || !d_signal || NP <= 0 ||
         NP % 32)
         return fail(DFN_E_ARG, "dfn_signal_grad: bad argument (NP must be a multiple of 32)");
@@ -1083,11 +1128,13 @@ int dfn_encode_signal_torso_bwd_set(const float* att_params, const float* poses,
 
 int dfn_decoder_fwd(int tier, int field, const void* packed, const float* bias, const float* points,
                     const float* dirs, long n, float* feat, float* sigma, void* stream) {
+    int width;
+    if (take_width(tier, width, "dfn_decoder_fwd") != DFN_OK) return DFN_E_ARG;
     if (!tier_ok(tier) || !field_ok(field) || !packed || !bias || !points || !dirs || !feat || !sigma)
         return fail(DFN_E_ARG, "dfn_decoder_fwd: bad argument");
     if (n <= 0) return DFN_OK;
     ProgramInfo pi;
-    program_info(tier, prog_field(field), &pi);
+    program_info(tier, prog_field(field), &pi, width);
     DecoderArgs A;
     A.wblob = (const char*)packed;
     A.nslab = pi.n_slabs;
@@ -1102,7 +1149,7 @@ int dfn_decoder_fwd(int tier, int field, const void* packed, const float* bias, 
     A.samples = nullptr;
     A.act_T = nullptr;
     A.masks = nullptr;
-    hipError_t err = launch_decoder(tier, A, (hipStream_t)stream);
+    hipError_t err = launch_decoder(tier, A, (hipStream_t)stream, width);
     if (err != hipSuccess) return hip_fail(err, "decoder_kernel");
     return DFN_OK;
 }
@@ -1110,6 +1157,7 @@ int dfn_decoder_fwd(int tier, int field, const void* packed, const float* bias, 
 int dfn_decoder_train_fwd(int tier, int field, const void* packed, const float* bias, const float* points,
                           const float* dirs, long n, float* feat, float* sigma, float* samples, void* act_T,
                           uint32_t* masks, void* stream) {
+    if (no_width(tier, "dfn_decoder_train_fwd") != DFN_OK) return DFN_E_ARG;
     if (!train_tier_ok(tier) || !train_field_ok(field) || !packed || !bias || !points ||
         !dirs || !feat || !sigma || !samples || !act_T || !masks)
         return fail(DFN_E_ARG, "dfn_decoder_train_fwd: bad argument (tiers f32 / bf16, fields head / torso / listener)");
@@ -1219,6 +1267,7 @@ int dfn_to8b(const float* x, long n, uint8_t* out, void* stream) {
 
 int dfn_debug_mfma_chain(int tier, int lds_reads_per_2, int valu_per_2, const void* fragments, const void* operands_b, int iters,
                          int blocks, float* out, uint64_t* clock, void* stream) {
+    if (no_width(tier, "dfn_debug_mfma_chain") != DFN_OK) return DFN_E_ARG;
     if ((tier != DFN_TIER_BF16 && tier != DFN_TIER_F16) || !fragments || !operands_b || !out || !clock || iters <= 0 || blocks <= 0)
         return fail(DFN_E_ARG, "dfn_debug_mfma_chain: bad argument");
     hipError_t err = launch_mfma_chain(tier == DFN_TIER_F16, lds_reads_per_2, valu_per_2, fragments, operands_b, iters, blocks, out,

@@ -34,6 +34,9 @@ enum Tier : int { TIER_F32 = 0, TIER_BF16 = 1, TIER_F16 = 2, TIER_F16X3 = 3 };
 //          hi fragment followed by a lo' fragment, and three v_mfma_f32_32x32x16_f16 (hi.hi, hi.lo', lo'.hi; lo'.lo' dropped):
 //          ~22-bit products, f32 accumulation.  16-bit in its fragment map (tier_frag16), f32 in everything else (tier_is16 is
 //          false: positional encoding, epilogue arithmetic, one wave per SIMD like the f32 tier).  Inference only.
+// the width flag of the C ABI (include/dfanerf.h: DFN_WIDTH_128), or'ed into a tier where one argument carries both (the kernels'
+// first template argument): the 128-wide inference program
+constexpr int TIER_W128 = 0x200, TIER_MASK = 0xff;
 DFN_HD constexpr bool tier_is16(int tier) { return tier == TIER_BF16 || tier == TIER_F16; }     // 16-bit operand arithmetic
 DFN_HD constexpr bool tier_frag16(int tier) { return tier != TIER_F32; }                       // 16-bit fragment map (E = 8)
 DFN_HD constexpr int tier_split(int tier) { return tier == TIER_F16X3 ? 2 : 1; }                // fragments per k-unit and tile

@@ -1177,14 +1177,19 @@ DFN_DEV void posenc(Vec<TIER, NT>& v, const float (&p)[3], int half) {
 //   head : IN(PE) | L1 L2 L3 | L4+SKIP(PE) | L5 L6 L7 | VIEW(act+view, 9 tiles) | OUT(1 tile)
 //   torso: E0 S0 (PE) | E1 S1 E2 S2 | E3+ESKIP(PE) S3 | E4 S4 | EO SO | IN(pd) | L1..L3 | L4+SKIP(pd) |
 //          L5..L7 | VIEW | OUT
-template <int TIER> struct Prog {
+// HT = hidden tiles: 8 = the 256-wide program (every tier, training included); 4 = the 128-wide inference program
+// (DFN_WIDTH_128: f32 / f16 / f16x3) - the same op order with 4 output tiles per trunk layer and half-length K over the
+// hidden vector.  The bias blob is the SAME for both (256-float strides): the narrow program reads the first 128 entries of
+// each hidden-sized vector.
+template <int TIER, int HT = 8> struct Prog {
+    static_assert(HT == 8 || HT == 4, "hidden tiles: 8 (256 wide) or 4 (128 wide)");
     static constexpr int UPT = TierCfg<TIER>::UPT;
-    static constexpr int KU_PE = 2 * UPT, KU_VIEW = UPT, KU_ACT = 8 * UPT, KU_D = 2 * UPT, KU_PD = 4 * UPT;
+    static constexpr int KU_PE = 2 * UPT, KU_VIEW = UPT, KU_ACT = HT * UPT, KU_D = 2 * UPT, KU_PD = 4 * UPT;
     static constexpr int FS = tier_split(TIER);         // fragments per (k-unit, tile): 2 in the f16x3 tier (hi, lo')
-    static constexpr int F_LAYER = 8 * KU_ACT * FS;     // fragments of one 256x256 layer (multiple of 32)
-    static constexpr int F_TAIL = (9 * (KU_ACT + KU_VIEW) + KU_ACT) * FS;
+    static constexpr int F_LAYER = HT * KU_ACT * FS;    // fragments of one hidden x hidden layer (multiple of 32)
+    static constexpr int F_TAIL = ((HT + 1) * (KU_ACT + KU_VIEW) + KU_ACT) * FS;
     // head
-    static constexpr int H_FRAGS = 8 * KU_PE * FS + 7 * F_LAYER + 8 * KU_PE * FS + F_TAIL;
+    static constexpr int H_FRAGS = HT * KU_PE * FS + 7 * F_LAYER + HT * KU_PE * FS + F_TAIL;
     static constexpr int H_SLABS = (H_FRAGS + SLAB_FRAGS - 1) / SLAB_FRAGS;
     // head bias blob (floats): in(256) L1..L4(4x256) skip(256) L5..L7(3x256) view(288) out(32)
     static constexpr int H_B_IN = 0, H_B_L1 = 256, H_B_SKIP = 5 * 256, H_B_L5 = 6 * 256, H_B_VIEW = 9 * 256,
@@ -1192,7 +1197,7 @@ template <int TIER> struct Prog {
     // torso
     static constexpr int F_D = 2 * KU_D * FS;           // fragments of one 64x64 layer
     static constexpr int T_F_DEFORM = 4 * KU_PE * FS + 10 * F_D + 2 * KU_PE * FS;   // E0 S0 | 10 64x64 layers | ESKIP
-    static constexpr int T_FRAGS = T_F_DEFORM + 8 * KU_PD * FS + 7 * F_LAYER + 8 * KU_PD * FS + F_TAIL;
+    static constexpr int T_FRAGS = T_F_DEFORM + HT * KU_PD * FS + 7 * F_LAYER + HT * KU_PD * FS + F_TAIL;
     static constexpr int T_SLABS = (T_FRAGS + SLAB_FRAGS - 1) / SLAB_FRAGS;
     // torso bias blob: E0 S0 E1 S1 E2 S2 E3 ESKIP S3 SSKIP E4 S4 EO SO (14 x 64), then the trunk like head
     static constexpr int T_B_E0 = 0, T_B_S0 = 64, T_B_E1 = 128, T_B_S1 = 192, T_B_E2 = 256, T_B_S2 = 320,
@@ -1233,12 +1238,13 @@ DFN_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // shared trunk: L1..L3, L4+skip, L5..L7, view layer, rgb head.  `act` holds relu(first layer) on entry;
 // f_l1 is the slab phase (fragment index mod 32) at L1.
-template <int TIER, int NTP, int KUP, class CT>
-DFN_DEV MlpOut mlp_trunk(Vec<TIER, 8>& act, const Vec<TIER, NTP>& pvec, const DhatRef& dref,
+// HT (deduced from `act`): hidden tiles, Prog<TIER, HT>.
+template <int TIER, int NTP, int KUP, int HT, class CT>
+DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const DhatRef& dref,
                          const lds_f32* bias, int b_l1, int b_skip, int b_l5, int b_view, int b_out,
                          int f_l1, Fetch<TIER>& fe, Stream& s, const CT& c, int r_trunk, int m_trunk) {
-    using P = Prog<TIER>;
-    Vec<TIER, 8> nxt;
+    using P = Prog<TIER, HT>;
+    Vec<TIER, HT> nxt;
     // blocks[0..6] with the skip after blocks[3] (decoder.py:313-325), ping-ponging between the two operand vectors:
     // the trunk's output a7 ends up in `nxt`.  Every layer starts at the same slab phase f_l1 (a layer is 128 fragments,
     // the skip adds a multiple of 32).  DFN_TRUNK_UNROLL: see below.
@@ -1246,43 +1252,64 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, 8>& act, const Vec<TIER, NTP>& pvec, const Dh
     const auto blk_row = [&](int k) { return r_trunk + RecMap::T_A0 + 256 * (k + 1); };          // output of blocks[k]
     const auto blk_mask = [&](int k) { return m_trunk + (k < 4 ? RecMap::TM_A0 + 4 * (k + 1) : RecMap::TM_A5 + 4 * (k - 4)); };
     int f = f_l1;
+    // "Every layer starts at the same slab phase" needs a layer AND the skip's extra group to be whole slabs.  In the 128-wide
+    // program (HT = 4) a 16-bit layer is 32 fragments but the HEAD's skip adds 4 x KU_PE = 16: the layers behind it start at
+    // phase f_l1 + 16.  That one trunk runs straight-line with the TRUE running fragment index (`f` is never reset); every other
+    // one (the torso's skip adds 32, the f32 / f16x3 tiers double everything) keeps the forms below.
+    constexpr bool SAME_PHASE = P::F_LAYER % SLAB_FRAGS == 0 && (HT * KUP * P::FS) % SLAB_FRAGS == 0;
+    static_assert(SAME_PHASE || HT != 8, "the 256-wide program resets the fragment index per layer");
+    static_assert(P::F_LAYER % PF_DEPTH == 0 && (HT * KUP * P::FS) % PF_DEPTH == 0, "register ring turns");
+    constexpr bool STRAIGHT = (DFN_TRUNK_UNROLL != 0) || !SAME_PHASE;
+    if constexpr (!SAME_PHASE) {
+        static_assert(!CT::rec_on, "the 128-wide program is inference only (no recorder rows for it)");
+#define DFN_PLAIN(OUT, IN, K) layer<TIER, HT, P::KU_ACT, HT, true>(OUT, IN, blk_bias(K), f, fe, s, c)
+        DFN_PLAIN(nxt, act, 0);
+        DFN_PLAIN(act, nxt, 1);
+        DFN_PLAIN(nxt, act, 2);
+        layer_skip<TIER, HT, P::KU_ACT, HT, KUP, NTP>(act, nxt, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c);
+        DFN_PLAIN(nxt, act, 4);
+        DFN_PLAIN(act, nxt, 5);
+        DFN_PLAIN(nxt, act, 6);
+#undef DFN_PLAIN
+    } else {
 #if DFN_TRUNK_UNROLL
     // straight-line: seven layer bodies, the operand vectors alternate by name (no copies, no loop-carried vectors)
-#define DFN_PLAIN(OUT, IN, K) f = f_l1; layer<TIER, 8, P::KU_ACT, 8, true>(OUT, IN, blk_bias(K), f, fe, s, c, blk_row(K), blk_mask(K))
+#define DFN_PLAIN(OUT, IN, K) f = f_l1; layer<TIER, HT, P::KU_ACT, HT, true>(OUT, IN, blk_bias(K), f, fe, s, c, blk_row(K), blk_mask(K))
     DFN_PLAIN(nxt, act, 0);
     DFN_PLAIN(act, nxt, 1);
     DFN_PLAIN(nxt, act, 2);
     f = f_l1;       // blocks[3], then the skip: relu(.) + fc_z_skips(z) + fc_p_skips(p)   (decoder.py:316-325)
-    layer_skip<TIER, 8, P::KU_ACT, 8, KUP, NTP>(act, nxt, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c,
-                                                r_trunk + RecMap::T_A0 + 256 * 4, m_trunk + RecMap::TM_A4R);
+    layer_skip<TIER, HT, P::KU_ACT, HT, KUP, NTP>(act, nxt, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c,
+                                                  r_trunk + RecMap::T_A0 + 256 * 4, m_trunk + RecMap::TM_A4R);
     DFN_PLAIN(nxt, act, 4);
     DFN_PLAIN(act, nxt, 5);
     DFN_PLAIN(nxt, act, 6);
 #undef DFN_PLAIN
 #else
-    // runtime loops (one layer body each): the 64-register copy after every layer is the price of the small code
+    // runtime loops (one layer body each): the copy of the operand vector after every layer is the price of the small code
     for (int l = 0; l < 3; ++l) {
         f = f_l1;
-        layer<TIER, 8, P::KU_ACT, 8, true>(nxt, act, bias + b_l1 + 256 * l, f, fe, s, c,
-                                           r_trunk + RecMap::T_A0 + 256 * (l + 1), m_trunk + RecMap::TM_A0 + 4 * (l + 1));
+        layer<TIER, HT, P::KU_ACT, HT, true>(nxt, act, bias + b_l1 + 256 * l, f, fe, s, c,
+                                             r_trunk + RecMap::T_A0 + 256 * (l + 1), m_trunk + RecMap::TM_A0 + 4 * (l + 1));
         act = nxt;
     }
     f = f_l1;       // blocks[3], then the skip: relu(.) + fc_z_skips(z) + fc_p_skips(p)   (decoder.py:316-325)
-    layer_skip<TIER, 8, P::KU_ACT, 8, KUP, NTP>(nxt, act, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c,
-                                                r_trunk + RecMap::T_A0 + 256 * 4, m_trunk + RecMap::TM_A4R);
+    layer_skip<TIER, HT, P::KU_ACT, HT, KUP, NTP>(nxt, act, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c,
+                                                  r_trunk + RecMap::T_A0 + 256 * 4, m_trunk + RecMap::TM_A4R);
     act = nxt;
     for (int l = 0; l < 3; ++l) {
         f = f_l1;
-        layer<TIER, 8, P::KU_ACT, 8, true>(nxt, act, bias + b_l5 + 256 * l, f, fe, s, c,
-                                           r_trunk + RecMap::T_A0 + 256 * (5 + l), m_trunk + RecMap::TM_A5 + 4 * l);
+        layer<TIER, HT, P::KU_ACT, HT, true>(nxt, act, bias + b_l5 + 256 * l, f, fe, s, c,
+                                             r_trunk + RecMap::T_A0 + 256 * (5 + l), m_trunk + RecMap::TM_A5 + 4 * l);
         act = nxt;
     }
 #endif
+    }
     // the trunk's output a7: in `nxt` after the straight-line form, in `act` after the loops; the other vector takes the
     // view layer's output
-    Vec<TIER, 8>& a7 = DFN_TRUNK_UNROLL ? nxt : act;
-    Vec<TIER, 8>& hid = DFN_TRUNK_UNROLL ? act : nxt;
-    // feat_view (+ sigma_out as row 0 of a 9th tile) on [act ; view PE]   (decoder.py:329-340)
+    Vec<TIER, HT>& a7 = STRAIGHT ? nxt : act;
+    Vec<TIER, HT>& hid = STRAIGHT ? act : nxt;
+    // feat_view (+ sigma_out as row 0 of a further tile) on [act ; view PE]   (decoder.py:329-340)
     MlpOut o;
     {
         Vec<TIER, 1> vview;
@@ -1297,21 +1324,21 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, 8>& act, const Vec<TIER, NTP>& pvec, const Dh
             pend = false;
         };
 #pragma unroll
-        for (int tg = 0; tg < 4; ++tg) {
+        for (int tg = 0; tg < HT / 2; ++tg) {
             f32x16 acc[2];
             acc_init<2>(acc, bias + b_view + tg * 64, c.half);
-            gemm_group<TIER, 2, P::KU_ACT, 8>(acc, a7, f, fe, s, c, flush);
+            gemm_group<TIER, 2, P::KU_ACT, HT>(acc, a7, f, fe, s, c, flush);
             gemm_group<TIER, 2, P::KU_VIEW, 1>(acc, vview, f, fe, s, c, flush);
             flush();
-            acc_to_vec<TIER, 2, 8, true>(acc, hid, 2 * tg);
-            if constexpr (tier_is16(TIER)) rec_mask_pair_packed<TIER, 8>(c, m_trunk + RecMap::TM_H + tg, hid, 2 * tg);
+            acc_to_vec<TIER, 2, HT, true>(acc, hid, 2 * tg);
+            if constexpr (tier_is16(TIER)) rec_mask_pair_packed<TIER, HT>(c, m_trunk + RecMap::TM_H + tg, hid, 2 * tg);
             else rec_mask_pair(c, m_trunk + RecMap::TM_H + tg, acc);
             pend = CT::rec_on;
             ptg = tg;
         }
         f32x16 acc1[1];
         acc_init<1>(acc1, bias + b_view + 256, c.half);
-        gemm_group<TIER, 1, P::KU_ACT, 8>(acc1, a7, f, fe, s, c, flush);
+        gemm_group<TIER, 1, P::KU_ACT, HT>(acc1, a7, f, fe, s, c, flush);
         gemm_group<TIER, 1, P::KU_VIEW, 1>(acc1, vview, f, fe, s, c, flush);
         flush();
         o.sigma = acc1[0][0];
@@ -1320,7 +1347,7 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, 8>& act, const Vec<TIER, NTP>& pvec, const Dh
     {
         f32x16 acc1[1];
         acc_init<1>(acc1, bias + b_out, c.half);
-        gemm_group<TIER, 1, P::KU_ACT, 8, 0>(acc1, hid, f, fe, s, c);     // last op of the pass
+        gemm_group<TIER, 1, P::KU_ACT, HT, 0>(acc1, hid, f, fe, s, c);    // last op of the pass
         o.r = sigmoidf_(acc1[0][0]);
         o.g = sigmoidf_(acc1[0][1]);
         o.b = sigmoidf_(acc1[0][2]);
@@ -1329,28 +1356,28 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, 8>& act, const Vec<TIER, NTP>& pvec, const Dh
 }
 
 // ---- head pass: decoder.py:291-349 with head_or_torso == 'head' ----------------------------------------------
-template <int TIER, class CT>
+template <int TIER, int HT = 8, class CT>
 DFN_DEV MlpOut mlp_head(const float (&p)[3], const DhatRef& dhat, const lds_f32* bias, Stream& s,
                         const CT& c) {
-    using P = Prog<TIER>;
+    using P = Prog<TIER, HT>;
     Vec<TIER, 2> pe;
     posenc<TIER, 2, NPE>(pe, p, c.half);
     rec_vec<TIER, 2>(c, RecMap::H_PE, pe);
-    Vec<TIER, 8> act;
+    Vec<TIER, HT> act;
     int f = 0;
     Fetch<TIER> fe;
     fe.prime(s, c);
-    layer<TIER, 8, P::KU_PE, 2, true>(act, pe, bias + P::H_B_IN, f, fe, s, c, RecMap::H_TRUNK + RecMap::T_A0,
+    layer<TIER, HT, P::KU_PE, 2, true>(act, pe, bias + P::H_B_IN, f, fe, s, c, RecMap::H_TRUNK + RecMap::T_A0,
                                       RecMap::H_MTRUNK + RecMap::TM_A0);
     return mlp_trunk<TIER, 2, P::KU_PE>(act, pe, dhat, bias, P::H_B_L1, P::H_B_SKIP, P::H_B_L5, P::H_B_VIEW,
                                         P::H_B_OUT, f % SLAB_FRAGS, fe, s, c, RecMap::H_TRUNK, RecMap::H_MTRUNK);
 }
 
 // ---- torso pass: deformation field (decoder.py:109-134, 297-299) then the trunk ---------------------------
-template <int TIER, class CT>
+template <int TIER, int HT = 8, class CT>
 DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32* bias, Stream& s,
                          const CT& c) {
-    using P = Prog<TIER>;
+    using P = Prog<TIER, HT>;
     Vec<TIER, 2> pe;
     posenc<TIER, 2, NPE>(pe, p, c.half);
     rec_vec<TIER, 2>(c, RecMap::S_PE, pe);
@@ -1400,8 +1427,8 @@ DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32
         for (int L = 0; L < 32; ++L) pd.set(32 + L, acc[L >> 4][L & 15]);
     }
     rec_vec<TIER, 4>(c, RecMap::S_PD, pd);
-    Vec<TIER, 8> act;
-    layer<TIER, 8, P::KU_PD, 4, true>(act, pd, bias + P::T_B_IN, f, fe, s, c, RecMap::S_TRUNK + RecMap::T_A0,
+    Vec<TIER, HT> act;
+    layer<TIER, HT, P::KU_PD, 4, true>(act, pd, bias + P::T_B_IN, f, fe, s, c, RecMap::S_TRUNK + RecMap::T_A0,
                                       RecMap::S_MTRUNK + RecMap::TM_A0);
     return mlp_trunk<TIER, 4, P::KU_PD>(act, pd, dhat, bias, P::T_B_L1, P::T_B_SKIP, P::T_B_L5, P::T_B_VIEW,
                                         P::T_B_OUT, f % SLAB_FRAGS, fe, s, c, RecMap::S_TRUNK, RecMap::S_MTRUNK);

@@ -51,8 +51,9 @@ struct DecoderArgs {
     unsigned* masks;
 };
 
-hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st);
-hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st);
-void program_info(int tier, int field, ProgramInfo* out);
+// width: 256 = the padded program of every tier; 128 = the 128-wide inference program (DFN_WIDTH_128: f32 / f16 / f16x3)
+hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width = 256);
+hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st, int width = 256);
+void program_info(int tier, int field, ProgramInfo* out, int width = 256);
 
 }  // namespace dfn

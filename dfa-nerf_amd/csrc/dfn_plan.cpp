@@ -101,16 +101,17 @@ ColFn ident(int ncols, int col0 = 0) {
 }
 
 // the trunk shared by all fields: L1..L3, L4+skip, L5..L7, view(+sigma), out
-void emit_trunk(Builder& b, int UPT, int pid_pskip, int KU_P, const ColFn& pcols) {
-    const int KU_ACT = 8 * UPT, KU_VIEW = UPT;
-    const ColFn act = ident(HID);
+// HT = hidden tiles (dfn_mlp.h Prog<TIER, HT>): 8, or 4 for the 128-wide program
+void emit_trunk(Builder& b, int UPT, int HT, int pid_pskip, int KU_P, const ColFn& pcols) {
+    const int KU_ACT = HT * UPT, KU_VIEW = UPT;
+    const ColFn act = ident(32 * HT);
     const int blk[7] = {P_BLK0_W, P_BLK1_W, P_BLK2_W, P_BLK3_W, P_BLK4_W, P_BLK5_W, P_BLK6_W};
-    for (int l = 0; l < 3; ++l) b.emit_layer(8, KU_ACT, rows_of(blk[l]), act);
-    b.emit_layer_skip(8, KU_ACT, rows_of(blk[3]), act, KU_P, rows_of(pid_pskip), pcols);
-    for (int l = 4; l < 7; ++l) b.emit_layer(8, KU_ACT, rows_of(blk[l]), act);
-    // view layer: 4 pairs of feat_view rows, each [act segment, view segment]; then the sigma tile
+    for (int l = 0; l < 3; ++l) b.emit_layer(HT, KU_ACT, rows_of(blk[l]), act);
+    b.emit_layer_skip(HT, KU_ACT, rows_of(blk[3]), act, KU_P, rows_of(pid_pskip), pcols);
+    for (int l = 4; l < 7; ++l) b.emit_layer(HT, KU_ACT, rows_of(blk[l]), act);
+    // view layer: HT / 2 pairs of feat_view rows, each [act segment, view segment]; then the sigma tile
     const ColFn view = [](int s) { return view_slot_to_ref(s); };
-    for (int tg = 0; tg < 4; ++tg) {
+    for (int tg = 0; tg < HT / 2; ++tg) {
         b.emit_group(2, 64 * tg, KU_ACT, rows_of(P_FEATV_W), act);
         b.emit_group(2, 64 * tg, KU_VIEW, rows_of(P_FCV_W), view);
     }
@@ -278,17 +279,18 @@ long build_bwd_plan(int tier, int field, std::vector<int32_t>& plan) {
     return n_frags;
 }
 
-long build_pack_plan(int tier, int field, std::vector<int32_t>& plan) {
+long build_pack_plan(int tier, int field, std::vector<int32_t>& plan, int width) {
     plan.clear();
     Builder b{tier, plan};
     const int UPT = tier_UPT(tier);
+    const int HT = width == 128 ? 4 : 8;
     const int KU_PE = 2 * UPT, KU_D = 2 * UPT, KU_PD = 4 * UPT;
     const ColFn pe = [](int s) { return pe_slot_to_ref(s); };
     if (field == FIELD_HEAD || field == 2 /* listener */) {
         const int pid_in = field == FIELD_HEAD ? P_FCIN_W : P_FCINL_W;
         const int pid_sk = field == FIELD_HEAD ? P_FCPSK_W : P_FCPSKL_W;
-        b.emit_layer(8, KU_PE, rows_of(pid_in), pe);
-        emit_trunk(b, UPT, pid_sk, KU_PE, pe);
+        b.emit_layer(HT, KU_PE, rows_of(pid_in), pe);
+        emit_trunk(b, UPT, HT, pid_sk, KU_PE, pe);
     } else {
         const ColFn d64 = ident(DH);
         b.emit_layer(2, KU_PE, rows_of(P_DE0_W), pe);                      // E0
@@ -309,8 +311,8 @@ long build_pack_plan(int tier, int field, std::vector<int32_t>& plan) {
             if (s >= 64 && s < 64 + NET) return NPE + (s - 64);
             return -1;
         };
-        b.emit_layer(8, KU_PD, rows_of(P_FCINT_W), pd);
-        emit_trunk(b, UPT, P_FCPSKT_W, KU_PD, pd);
+        b.emit_layer(HT, KU_PD, rows_of(P_FCINT_W), pd);
+        emit_trunk(b, UPT, HT, P_FCPSKT_W, KU_PD, pd);
     }
     // pad to whole slabs (the kernel always DMA-loads whole slabs)
     const long frag_elems = 64L * tier_E(tier);

@@ -1,5 +1,6 @@
-// dfn_render.hip - tier dispatch of the fused frame renderer and the fused decoder.
-// The kernels are templates in dfn_render_kernels.h, instantiated per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip.
+// dfn_render.hip - tier and width dispatch of the fused frame renderer and the fused decoder.
+// The kernels are templates in dfn_render_kernels.h, instantiated per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip
+// and, for the 128-wide inference program (DFN_WIDTH_128), in dfn_render_{f32,f16,f16x3}_w128.hip.
 #include <hip/hip_runtime.h>
 #include "dfn_layout.h"
 #include "dfn_mlp.h"
@@ -15,8 +16,22 @@ hipError_t launch_decoder_f32(const DecoderArgs& A, hipStream_t st);
 hipError_t launch_decoder_bf16(const DecoderArgs& A, hipStream_t st);
 hipError_t launch_decoder_f16(const DecoderArgs& A, hipStream_t st);
 hipError_t launch_decoder_f16x3(const DecoderArgs& A, hipStream_t st);
+hipError_t launch_render_f32_w128(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16_w128(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16x3_w128(const RenderArgs& A, hipStream_t st);
+hipError_t launch_decoder_f32_w128(const DecoderArgs& A, hipStream_t st);
+hipError_t launch_decoder_f16_w128(const DecoderArgs& A, hipStream_t st);
+hipError_t launch_decoder_f16x3_w128(const DecoderArgs& A, hipStream_t st);
 
-hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st) {
+hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width) {
+    if (width == 128) {
+        switch (tier) {
+        case TIER_F32: return launch_render_f32_w128(A, st);
+        case TIER_F16: return launch_render_f16_w128(A, st);
+        case TIER_F16X3: return launch_render_f16x3_w128(A, st);
+        default: return hipErrorInvalidValue;      // (bf16: the training tier stays padded; the API refuses it before)
+        }
+    }
     switch (tier) {
     case TIER_BF16: return launch_render_bf16(A, st);
     case TIER_F16: return launch_render_f16(A, st);
@@ -24,7 +39,15 @@ hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st) {
     default: return launch_render_f32(A, st);
     }
 }
-hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st) {
+hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st, int width) {
+    if (width == 128) {
+        switch (tier) {
+        case TIER_F32: return launch_decoder_f32_w128(A, st);
+        case TIER_F16: return launch_decoder_f16_w128(A, st);
+        case TIER_F16X3: return launch_decoder_f16x3_w128(A, st);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (tier) {
     case TIER_BF16: return launch_decoder_bf16(A, st);
     case TIER_F16: return launch_decoder_f16(A, st);
@@ -34,7 +57,18 @@ hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st) {
 }
 
 // the 16-bit tiers share one program (same fragment counts and bias blob)
-void program_info(int tier, int field, ProgramInfo* out) {
+template <class P> static ProgramInfo info_of(int field) {
+    return field == FIELD_TORSO ? ProgramInfo{P::T_FRAGS, P::T_SLABS, P::T_NBIAS} : ProgramInfo{P::H_FRAGS, P::H_SLABS, P::H_NBIAS};
+}
+void program_info(int tier, int field, ProgramInfo* out, int width) {
+    if (width == 128) {             // the 128-wide inference program: fewer fragments, the SAME bias blob
+        static_assert(Prog<TIER_F16, 4>::H_FRAGS == 314 && Prog<TIER_F16, 4>::T_FRAGS == 450, "128-wide 16-bit stream");
+        static_assert(Prog<TIER_F16X3, 4>::H_FRAGS == 2 * 314 && Prog<TIER_F16X3, 4>::T_FRAGS == 2 * 450, "128-wide f16x3 stream");
+        static_assert(Prog<TIER_F32, 4>::H_NBIAS == Prog<TIER_F32>::H_NBIAS && Prog<TIER_F16, 4>::T_NBIAS == Prog<TIER_F16>::T_NBIAS, "bias blob");
+        *out = tier == TIER_F16X3 ? info_of<Prog<TIER_F16X3, 4>>(field)
+               : tier == TIER_F32 ? info_of<Prog<TIER_F32, 4>>(field) : info_of<Prog<TIER_F16, 4>>(field);
+        return;
+    }
     if (tier == TIER_F16X3) {       // the f16 program with two fragments (hi, lo') per k-unit and tile; the same bias blob
         using P = Prog<TIER_F16X3>;
         static_assert(P::H_FRAGS == 2 * Prog<TIER_F16>::H_FRAGS && P::T_FRAGS == 2 * Prog<TIER_F16>::T_FRAGS, "f16x3 stream");

@@ -1,6 +1,7 @@
 // dfn_render_kernels.h - fused frame renderer and fused decoder for gfx950 (MI355X): the kernel templates.
-// Instantiated once per precision tier in dfn_render_{f32,bf16,f16}.hip (separate translation units: they build
-// in parallel); dfn_render.hip dispatches on the tier.
+// Instantiated once per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip and, for the 128-wide inference program, in
+// dfn_render_{f32,f16,f16x3}_w128.hip (separate translation units: they build in parallel); dfn_render.hip dispatches on
+// the tier and the width.
 //
 // One wavefront = one ray.  A workgroup of W waves (8 in the bf16 tier, 4 in the f32 tier) walks W rays
 // through: ray generation -> 64 coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
@@ -140,12 +141,18 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // order; the backward gets the merged depths and each point's merged rank to composite them in depth order)
 // ACT4 (training forwards only): the recorder writes act_T as MX-fp4 (the default of the fused step) or as MX-fp8 e4m3 (the
 // run-time opt-out: DFN_TRAIN_ACT_E4M3 or'ed into the tier of the dfn_train_fwd* calls; instantiated in dfn_render_bf16e.hip)
-template <int TIER, bool TWO, int TRAIN, bool ACT4 = true>
-__global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 256) void render_kernel(
+// TW: the tier, with the width flag of the C ABI or'ed in (TIER_W128 == DFN_WIDTH_128: the 128-wide inference program, HT = 4 hidden
+// tiles - dfn_mlp.h Prog<TIER, HT>).  Only the MLP passes differ between the widths: sampler, compositing, epilogues, LDS layout, ring,
+// workgroup shape and block mapping are the same code.  (The flag rides in the tier argument here as it does in the ABI: the 256-wide
+// kernels keep their template arguments, hence their names and their ISA.)
+template <int TW, bool TWO, int TRAIN, bool ACT4 = true>
+__global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & TIER_MASK)>::THREADS / 256) void render_kernel(
     const RenderArgs A) {
+    constexpr int TIER = TW & TIER_MASK, HT = (TW & TIER_W128) ? 4 : 8;
+    static_assert(HT == 8 || TRAIN == 0, "the 128-wide program is inference only");
     using C = TierCfg<TIER>;
     using L = KernelLds<TIER, TWO>;
-    using P = Prog<TIER>;
+    using P = Prog<TIER, HT>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -343,10 +350,10 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
             const unsigned long long tm0 = __builtin_readcyclecounter();
 #endif
             if constexpr (std::is_same<CtxH, CtxK>::value) {
-                a = mlp_head<TIER>(p, dref_h, bias_h, s, ctx);
+                a = mlp_head<TIER, HT>(p, dref_h, bias_h, s, ctx);
             } else {
                 const CtxH ctx_h = {ctx.ring, ctx.wave, ctx.lane, ctx.half, ctx.rec};
-                a = mlp_head<TIER>(p, dref_h, bias_h, s, ctx_h);
+                a = mlp_head<TIER, HT>(p, dref_h, bias_h, s, ctx_h);
             }
 #ifdef DFN_TIMING
             T_mlp += __builtin_readcyclecounter() - tm0;
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
                 ctx.rec = {A.act_T[1], A.masks[1], RecMap::S_ROWS, rr * (S / 32) + (phase == PH_COARSE ? tile : 2 + tile),
                            RecMap::S_MDWORDS};
             }
-            b = mlp_torso<TIER>(p, dref_t, bias_t, s, ctx);
+            b = mlp_torso<TIER, HT>(p, dref_t, bias_t, s, ctx);
         }
 
         if (phase == PH_COARSE) {
@@ -686,9 +693,12 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
 // ================================================================================================
 // REC: the training recorder is on (dfn_decoder_train_fwd): every GEMM input, the ReLU bits and the raw outputs are
 // stored for the backward kernels, exactly as render_kernel<.., TRAIN> does for the points it generates itself.
-template <int TIER, bool TORSO, bool REC = false>
-__global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 256) void decoder_kernel(
+// TW: tier | width flag, as in render_kernel.
+template <int TW, bool TORSO, bool REC = false>
+__global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & TIER_MASK)>::THREADS / 256) void decoder_kernel(
     const DecoderArgs A) {
+    constexpr int TIER = TW & TIER_MASK, HT = (TW & TIER_W128) ? 4 : 8;
+    static_assert(HT == 8 || !REC, "the 128-wide program is inference only");
     using C = TierCfg<TIER>;
     using L = KernelLds<TIER>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -697,7 +707,9 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 31;
     lds_char* lds = (lds_char*)smem;
-    typedef CtxT<REC, false, REC> CtxD;
+    // (128-wide program: the asm fragment fetch, as in the render kernels - with the compiler's own reads the 16-bit torso kernel
+    // spills 96 VGPRs to scratch, which the build refuses; tools/check_inflight.py runs on these kernels too)
+    typedef CtxT<REC, HT != 8, REC> CtxD;
     CtxD ctx = {lds, wave, lane, lane >> 5, {}};
     ctx.rec.act_T = nullptr;
     ctx.rec.masks = nullptr;
@@ -737,8 +749,8 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
     if constexpr (REC)
         ctx.rec = {A.act_T, A.masks, torso ? RecMap::S_ROWS : RecMap::H_ROWS, tile, torso ? RecMap::S_MDWORDS : RecMap::H_MDWORDS};
     MlpOut o;
-    if constexpr (torso) o = mlp_torso<TIER>(p, dref, bias_l, s, ctx);
-    else o = mlp_head<TIER>(p, dref, bias_l, s, ctx);
+    if constexpr (torso) o = mlp_torso<TIER, HT>(p, dref, bias_l, s, ctx);
+    else o = mlp_head<TIER, HT>(p, dref, bias_l, s, ctx);
     if (lane < 32) {
         if (tile_raw < n_tiles && pt_raw < A.n_points) {
             A.feat[pt_raw * 3 + 0] = o.r;
@@ -754,35 +766,37 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- per-tier launchers (instantiated by dfn_render_<tier>.hip)
+// ---- per-tier launchers (instantiated by dfn_render_<tier>.hip; W128 = TIER_W128: the 128-wide program, dfn_render_<tier>_w128.hip)
 template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
-template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
+template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true, int W128 = 0> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
+    static_assert(W128 == 0 || (W128 == TIER_W128 && TRAIN == 0), "widths");
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER, TWO>::TOTAL;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = set_lds(render_kernel<TIER, TWO, TRAIN, ACT4>, lds);
+        hipError_t e = set_lds(render_kernel<TIER | W128, TWO, TRAIN, ACT4>, lds);
         if (e != hipSuccess) return e;
         attr_done = true;
     }
     const int blocks = (A.frame.ray_count + C::WAVES - 1) / C::WAVES;
-    hipLaunchKernelGGL((render_kernel<TIER, TWO, TRAIN, ACT4>), dim3(blocks), dim3(C::THREADS), lds, st, A);
+    hipLaunchKernelGGL((render_kernel<TIER | W128, TWO, TRAIN, ACT4>), dim3(blocks), dim3(C::THREADS), lds, st, A);
     return hipGetLastError();
 }
-template <int TIER, bool TORSO, bool REC = false> static hipError_t launch_decoder_t(const DecoderArgs& A, hipStream_t st) {
+template <int TIER, bool TORSO, bool REC = false, int W128 = 0> static hipError_t launch_decoder_t(const DecoderArgs& A, hipStream_t st) {
+    static_assert(W128 == 0 || (W128 == TIER_W128 && !REC), "widths");
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER>::TOTAL;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = set_lds(decoder_kernel<TIER, TORSO, REC>, lds);
+        hipError_t e = set_lds(decoder_kernel<TIER | W128, TORSO, REC>, lds);
         if (e != hipSuccess) return e;
         attr_done = true;
     }
     const long per_block = (long)C::WAVES * 32;
     const int blocks = (int)((A.n_points + per_block - 1) / per_block);
-    hipLaunchKernelGGL((decoder_kernel<TIER, TORSO, REC>), dim3(blocks), dim3(C::THREADS), lds, st, A);
+    hipLaunchKernelGGL((decoder_kernel<TIER | W128, TORSO, REC>), dim3(blocks), dim3(C::THREADS), lds, st, A);
     return hipGetLastError();
 }
 
@@ -798,6 +812,15 @@ template <int TIER, bool TRAINABLE> static hipError_t launch_render_tier(const R
         } else return hipErrorInvalidValue;
     }
     return two ? launch_render_t<TIER, true>(A, st) : launch_render_t<TIER, false>(A, st);
+}
+// the 128-wide program of one tier (inference only: the API refuses DFN_WIDTH_128 in every training entry point)
+template <int TIER> static hipError_t launch_render_tier_w128(const RenderArgs& A, hipStream_t st) {
+    if (A.samples_out) return hipErrorInvalidValue;
+    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, TIER_W128>(A, st) : launch_render_t<TIER, false, 0, true, TIER_W128>(A, st);
+}
+template <int TIER> static hipError_t launch_decoder_tier_w128(const DecoderArgs& A, hipStream_t st) {
+    if (A.act_T) return hipErrorInvalidValue;
+    return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true, false, TIER_W128>(A, st) : launch_decoder_t<TIER, false, false, TIER_W128>(A, st);
 }
 template <int TIER, bool TRAINABLE> static hipError_t launch_decoder_tier(const DecoderArgs& A, hipStream_t st) {
     if (A.act_T) {           // training forward on explicit points: recorder on

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("DFN_LIB") or os.path.join(_HERE, "libdfanerf.so")
 
 TIER_F32, TIER_BF16, TIER_F16, TIER_F16X3 = 0, 1, 2, 3
 TRAIN_ACT_E4M3 = 0x100      # or'ed into the tier of dfn_train_fwd*: e4m3 instead of e2m1 activations (include/dfanerf.h)
+WIDTH_128 = 0x200           # or'ed into the tier of the inference entry points: the 128-wide program (include/dfanerf.h: DFN_WIDTH_128)
+WIDTH_128_TIERS = (TIER_F32, TIER_F16, TIER_F16X3)      # (bf16 is the training tier and stays padded)
 ACT_E4M3, ACT_E2M1 = 0, 1
 FIELD_HEAD, FIELD_TORSO, FIELD_LISTENER = 0, 1, 2
 N_DECODER_PARAMS = 955242

@@ -120,7 +120,9 @@ class Decoder(nn.Module):
         return (0 if self.use_deformation_field else engine.N_DEFORM_PARAMS), [engine.padded_shape(k, sd[k].shape) for k in names]
 
     def packed(self, tier="bf16"):
-        """Kernel-ready weights for `tier`, repacked whenever a parameter has changed in place."""
+        """Kernel-ready weights for `tier`, repacked whenever a parameter has changed in place.  A decoder with hidden_size <= 128
+        gets the native 128-wide program in the inference tiers (engine.select_width; DFN_WIDTH=256 in the environment forces the
+        padded one - read when the pack is built)."""
         from . import engine
         if not self.hip_supported():
             raise NotImplementedError("the HIP path supports the scripts/test_obama.sh decoder configuration only")
@@ -131,7 +133,8 @@ class Decoder(nn.Module):
         hit = self._hip.get(tier)
         if hit is None or hit[1][1:] != stamp[1:]:
             flat = engine.flatten_state(self.state_dict(), params[0].device)
-            hit = (engine.PackedDecoder(flat, tier, fields=(0, 1, 2), z_dim=self.z_dim), stamp)
+            hit = (engine.PackedDecoder(flat, tier, fields=(0, 1, 2), z_dim=self.z_dim,
+                                        width=engine.select_width(self.hidden_size, tier)), stamp)
         elif hit[1][0] != stamp[0]:
             hit[0].flat.copy_(engine.flatten_state(self.state_dict(), params[0].device))
             hit[0].repack()

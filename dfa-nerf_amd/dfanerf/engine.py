@@ -4,13 +4,14 @@ PyTorch is plumbing here (device memory, the current HIP stream, torch.distribut
 render path comes out of the HIP kernels behind the C ABI (include/dfanerf.h).  Nothing in this module
 computes on the CPU and nothing falls back to ATen."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import (DECODER_UNUSED_PREFIXES, DfnFrame, FIELD_HEAD, FIELD_LISTENER, FIELD_TORSO, N_DECODER_PARAMS, TIER_BF16, TIER_F16, TIER_F16X3,
-                   TIER_F32, check, lib)
+                   TIER_F32, WIDTH_128, WIDTH_128_TIERS, check, lib)
 
 # "f16": v_mfma_f32_32x32x16_f16, the throughput tier (inference only); "bf16": also the 16-bit training tier;
 # "f16x3": split f16 operands (hi + 2^-11 lo', three f16 MFMAs per product), the f32 tier's accuracy in f16's range (inference only)
@@ -71,7 +72,9 @@ def flatten_state(state, device):
     only (the fold, dfn_fold_bias) - they enter the library's [256, 256] slots padded with zero columns, and the codes are padded with
     zeros to match (pad_z): W_pad . z_pad = W . z exactly (zero products add nothing in any summation order).
     --n_feat < 256: a hidden unit with zero weights and zero bias outputs relu(0) = 0 and feeds zero columns - the
-    network written out 256 wide is the same function, exactly (at the 256-wide network's cost).
+    network written out 256 wide is the same function, exactly.  (The flat vector is ALWAYS this 256-wide layout.  Inference of
+    --n_feat <= 128 packs and renders it with the 128-wide program - PackedDecoder(width=128), select_width - which skips the zero
+    rows and columns instead of multiplying them; wider networks and training run the 256-wide program at its cost.)
     (Training such decoders: training._FlatNet keeps the same padded layout; the padded entries get zero gradients - relu'(0) = 0 -
     and stay zero.)  A decoder WITHOUT --use_deformation_field: the torso evaluates `deform(p) + p` (decoder.py:297-299) with an all-zero
     deformation network - every layer of it returns exactly 0 (relu(0) = 0, bias 0), so `p` passes unchanged, bit for bit."""
@@ -95,22 +98,48 @@ def flatten_state(state, device):
     return flat
 
 
-class PackedDecoder:
-    """Kernel-ready weight streams of one decoder, per (tier, field).  Call repack() after an optimizer step."""
+def select_width(hidden_size, tier, force=None):
+    """Width of the decoder program that renders a `hidden_size`-wide decoder in `tier`: 128 (the native 128-wide inference
+    program, DFN_WIDTH_128) when hidden_size <= 128 and the tier is f32 / f16 / f16x3, else 256 (the padded program: wider
+    decoders, and bf16 - the training tier).  `force` (default: the environment variable DFN_WIDTH, read here, i.e. when the pack
+    is built): "256" forces the padded program - the A/B switch; "128" on a decoder or tier that has no narrow program raises."""
+    if force is None:
+        force = os.environ.get("DFN_WIDTH", "")
+    force = str(force).strip()
+    if force not in ("", "128", "256"):
+        raise ValueError(f"DFN_WIDTH={force!r}: 128 or 256")
+    native = int(hidden_size) <= 128 and TIERS[tier] in WIDTH_128_TIERS
+    if force == "128" and not native:
+        raise ValueError(f"DFN_WIDTH=128: the 128-wide program serves decoders with hidden_size <= 128 in the f32 / f16 / f16x3 tiers "
+                         f"(hidden_size {hidden_size}, tier {tier_name(tier)}): packing a wider network with it would truncate it")
+    return 128 if native and force != "256" else 256
 
-    def __init__(self, flat_params, tier="bf16", fields=(FIELD_HEAD, FIELD_TORSO), z_dim=256):
+
+class PackedDecoder:
+    """Kernel-ready weight streams of one decoder, per (tier, field).  Call repack() after an optimizer step.
+    width = 128: the 128-wide inference program (tiers f32 / f16 / f16x3) - every pack, fold, render and decoder call made through
+    this object carries DFN_WIDTH_128.  The CALLER vouches that `flat_params` (always the 256-padded layout) is zero beyond hidden
+    unit 128 (Decoder.packed does, from hidden_size): the narrow pack drops those entries."""
+
+    def __init__(self, flat_params, tier="bf16", fields=(FIELD_HEAD, FIELD_TORSO), z_dim=256, width=256):
+        if int(width) not in (128, 256):
+            raise ValueError(f"PackedDecoder: width {width} (128 or 256)")
+        if int(width) == 128 and TIERS[tier] not in WIDTH_128_TIERS:
+            raise ValueError(f"PackedDecoder: width 128 is an inference program of the f32 / f16 / f16x3 tiers, not of {tier_name(tier)}")
         require_gpu()
         if not 0 < int(z_dim) <= 256:
             raise ValueError(f"PackedDecoder: z_dim {z_dim} (1 ... 256)")
         self.z_dim = int(z_dim)         # width of the latent codes fold() is handed (padded with zeros to the library's 256)
         self.tier = TIERS[tier]
+        self.width = int(width)
+        self.tier_arg = self.tier | (WIDTH_128 if self.width == 128 else 0)      # the `tier` argument of the library calls
         self.flat = flat_params
         self.device = flat_params.device
         self.packed = {}
         self.f16_bounds = None          # f16 / f16x3 tier: calibrated max |activation| per layer (f16guard.activation_bounds), once known
         self.f16_weight_max = None
         for f in fields:
-            nbytes = check(lib.dfn_packed_bytes(self.tier, f), "dfn_packed_bytes")
+            nbytes = check(lib.dfn_packed_bytes(self.tier_arg, f), "dfn_packed_bytes")
             self.packed[f] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.repack()
 
@@ -122,10 +151,10 @@ class PackedDecoder:
             self.f16_weight_max = f16guard.weight_bound(self.flat)
             f16guard.check(None, self.f16_weight_max, what="a decoder parameter", tier=tier_name(self.tier))
         for f, buf in self.packed.items():
-            check(lib.dfn_pack_weights(self.tier, f, _ptr(self.flat), _ptr(buf), _stream()), "dfn_pack_weights")
+            check(lib.dfn_pack_weights(self.tier_arg, f, _ptr(self.flat), _ptr(buf), _stream()), "dfn_pack_weights")
 
     def bias_floats(self, field):
-        return check(lib.dfn_bias_floats(self.tier, field), "dfn_bias_floats")
+        return check(lib.dfn_bias_floats(self.tier_arg, field), "dfn_bias_floats")
 
     def fold(self, sig_head, sig_torso, z_shape, z_app, head_field=FIELD_HEAD, out=None):
         """Per-frame bias blob [head | torso].  z_shape / z_app: [2,256] rows (head, torso) or [256] for
@@ -137,12 +166,12 @@ class PackedDecoder:
             out = torch.empty(nh + nt, dtype=torch.float32, device=dev)
         zs, za = self.pad_z(z_shape), self.pad_z(z_app)
         sh = None if sig_head is None else _f32c(sig_head, dev).reshape(-1)
-        check(lib.dfn_fold_bias(self.tier, head_field, _ptr(self.flat), _ptr(sh), _ptr(zs[0]), _ptr(za[0]),
+        check(lib.dfn_fold_bias(self.tier_arg, head_field, _ptr(self.flat), _ptr(sh), _ptr(zs[0]), _ptr(za[0]),
                                 _ptr(out), _stream()), "dfn_fold_bias(head)")
         if nt:
             st = _f32c(sig_torso, dev).reshape(-1)
             row = 1 if zs.shape[0] > 1 else 0
-            check(lib.dfn_fold_bias(self.tier, FIELD_TORSO, _ptr(self.flat), _ptr(st), _ptr(zs[row]), _ptr(za[row]),
+            check(lib.dfn_fold_bias(self.tier_arg, FIELD_TORSO, _ptr(self.flat), _ptr(st), _ptr(zs[row]), _ptr(za[row]),
                                     C.c_void_p(out.data_ptr() + 4 * nh), _stream()), "dfn_fold_bias(torso)")
         return out
 
@@ -159,7 +188,7 @@ class PackedDecoder:
         sg = None if signal is None else _f32c(signal, dev).reshape(-1)
         zs = self.pad_z(z_shape).reshape(-1)
         za = self.pad_z(z_app).reshape(-1)
-        check(lib.dfn_fold_bias(self.tier, field, _ptr(self.flat), _ptr(sg), _ptr(zs), _ptr(za), _ptr(out),
+        check(lib.dfn_fold_bias(self.tier_arg, field, _ptr(self.flat), _ptr(sg), _ptr(zs), _ptr(za), _ptr(out),
                                 _stream()), "dfn_fold_bias")
         return out
 
@@ -340,7 +369,7 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
     if pix_index is not None:
         pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
-    check(lib.dfn_render_fwd(packed.tier, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+    check(lib.dfn_render_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
                              _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
                              _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h),
                              _ptr(w_c), _ptr(z_v), _stream()), "dfn_render_fwd")
@@ -370,7 +399,7 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
     bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
     if pix_index is not None:
         pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
-    check(lib.dfn_render_fwd_u8(packed.tier, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+    check(lib.dfn_render_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
                                 _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
                                 _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()),
           "dfn_render_fwd_u8")
@@ -387,7 +416,7 @@ def decoder_forward(packed, field, bias, points, dirs):
     sigma = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return feat, sigma
-    check(lib.dfn_decoder_fwd(packed.tier, field, _ptr(packed.packed[field]), _ptr(bias), _ptr(pts), _ptr(dr), n,
+    check(lib.dfn_decoder_fwd(packed.tier_arg, field, _ptr(packed.packed[field]), _ptr(bias), _ptr(pts), _ptr(dr), n,
                               _ptr(feat), _ptr(sigma), _stream()), "dfn_decoder_fwd")
     return feat, sigma
 

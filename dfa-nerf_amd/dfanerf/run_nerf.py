@@ -808,7 +808,9 @@ def check_supported(args):
     if args.dim_signal != 96:
         bad.append(f"--dim_signal {args.dim_signal} (supported: 96 - what the signal encoders emit, upstream too)")
     # --z_dim / --n_feat 1 ... 256 (upstream: free): a narrower network lives in the library's 256-wide layout with zero rows / columns -
-    # the same function exactly, forward and backward (engine.flatten_state, training._FlatNet) - at the 256-wide network's cost
+    # the same function exactly, forward and backward (engine.flatten_state, training._FlatNet).  Inference of --n_feat <= 128 runs
+    # natively on the 128-wide program (f32 / f16 / f16x3 tiers: Decoder.packed, engine.select_width); --n_feat 129 ... 255, the bf16
+    # tier and every training step stay padded, at the 256-wide network's cost
     if not 0 < args.z_dim <= 256:
         bad.append(f"--z_dim {args.z_dim} (supported: 1 ... 256)")
     if not 0 < args.n_feat <= 256:

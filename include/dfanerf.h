@@ -43,6 +43,22 @@ extern "C" {
                              * hi and a lo' fragment per k-unit: dfn_packed_bytes is twice the f16 tier's.  f16's range (|x| <= 65504).
                              * Inference entry points only, like DFN_TIER_F16: the training entry points return DFN_E_ARG for it. */
 
+/* DFN_WIDTH_128, or'ed into the `tier` argument: the 128-wide INFERENCE program - for a decoder whose hidden width (--n_feat) is
+ * <= 128: 4 output tiles per trunk layer and half-length K over the hidden vector, 314 instead of 1,138 MFMA fragments per head
+ * pass (16-bit tiers; torso 450 instead of 1,306).
+ *   - accepted with DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 by dfn_packed_bytes, dfn_pack_weights, dfn_pack_plan, dfn_render_fwd,
+ *     dfn_render_fwd_u8 and dfn_decoder_fwd; dfn_bias_floats and dfn_fold_bias accept and ignore it (the bias blob keeps its layout
+ *     and its 256-float strides: the narrow kernels read the first 128 entries of each hidden-sized vector);
+ *   - with DFN_TIER_BF16 (the training tier: it stays padded) and in every other entry point that takes a tier - the training
+ *     forwards, the backward streams and kernels, the gradient calls - the result is DFN_E_ARG, before any device work;
+ *   - `params` does not change: the 256-padded flat vector of DFN_N_DECODER_PARAMS floats.  The narrow plan references the same
+ *     entries, rows and columns below 128 of every hidden-sized tensor only.  PACKING A NETWORK WITH NON-ZERO ENTRIES BEYOND 128
+ *     UNDER THIS FLAG TRUNCATES IT: the caller vouches for the width.  For a network that is zero there, the narrow program returns
+ *     the padded program's results bit for bit (the dropped MFMAs are the all-zero trailing k-units of each activation segment, the
+ *     dropped output tiles feed zero columns only, and the order of the surviving terms is unchanged);
+ *   - a stream packed with the flag must be rendered with the flag (dfn_packed_bytes differs), and the other way round. */
+#define DFN_WIDTH_128 0x200
+
 #define DFN_FIELD_HEAD 0        /* DEC:303-305  fc_in / fc_p_skips       */
 #define DFN_FIELD_TORSO 1       /* DEC:297-299, 308-309, 324-325 deform_net + fc_in_torso / fc_p_skips_torso */
 #define DFN_FIELD_LISTENER 2    /* DEC:306-307, 322-323 fc_in_listener / fc_p_skips_listener (signal None) */
@@ -50,7 +66,8 @@ extern "C" {
 #define DFN_N_DECODER_PARAMS 955242
 
 const char* dfn_last_error(void);
-/* library build info: "dfanerf <version> gfx950".  ABI notes - 0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
+/* library build info: "dfanerf <version> gfx950".  ABI notes - DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
  * the workspace's per-slice partials in EVERY tier - dbias is written by dfn_weight_bias_grad_reduce (a caller of _partials alone gets
