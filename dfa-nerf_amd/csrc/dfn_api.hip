@@ -233,9 +233,9 @@ extern "C" {
 
 const char* dfn_last_error(void) { return g_err.c_str(); }
 #ifdef DFN_DEV_BUILD      // (dfn_devguard.h: a library built with developer switches says so, and dfanerf._lib refuses it in-tree)
-const char* dfn_version(void) { return "dfanerf 0.3 gfx950 DEV"; }
+const char* dfn_version(void) { return "dfanerf 0.4 gfx950 DEV"; }
 #else
-const char* dfn_version(void) { return "dfanerf 0.3 gfx950"; }
+const char* dfn_version(void) { return "dfanerf 0.4 gfx950"; }
 #endif
 
 long dfn_packed_bytes(int tier, int field) {
@@ -345,12 +345,22 @@ int dfn_adam_multi(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int 
     return DFN_OK;
 }
 
+// the per-ray outputs of an aux launch (dfn_render_fwd_aux: head / com = f32 [ray_count,2]; dfn_render_fwd_u8_aux: head / com =
+// alpha8, d16_* = depth16)
+struct AuxOut {
+    void *head, *com, *d16_head, *d16_com;
+};
 static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                            const float* bias_head, const float* bias_torso, const float* bg_f32,
                            const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
-                           float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream) {
+                           float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream,
+                           const AuxOut* aux = nullptr) {
     int width;
     if (take_width(tier, width, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
+    // the aux kernels exist in the inference tiers only (bf16 is the training tier)
+    if (aux && tier == DFN_TIER_BF16)
+        return fail(DFN_E_ARG, "dfn_render_fwd_aux: opacity / depth outputs exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
+                               "(bf16 is the training tier)");
     if (!tier_ok(tier) || !frame || !packed_head || !bias_head || !rgb_head)
         return fail(DFN_E_ARG, "dfn_render_fwd: bad argument");
     const DfnFrame& F = *frame;
@@ -388,8 +398,16 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
     A.w_com = weights_com;
     A.z_out = z_vals;
     A.out_u8 = out_u8;
+    A.aux = 0;
     A.samples_out = nullptr;
     A.ranks_out = nullptr;
+    if (aux) {       // the aux kernels write no per-sample output: its argument slots carry the per-ray ones (dfn_params.h)
+        A.aux = 1;
+        A.alpha8_head = (unsigned char*)aux->head;          // (= aux_head in the f32 form)
+        A.alpha8_com = (unsigned char*)aux->com;
+        A.depth16_head = (unsigned short*)aux->d16_head;
+        A.depth16_com = (unsigned short*)aux->d16_com;
+    }
     A.act_T[0] = A.act_T[1] = nullptr;
     A.masks[0] = A.masks[1] = nullptr;
     A.NP = 0;
@@ -414,6 +432,32 @@ int dfn_render_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, 
                       const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream) {
     return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
                            (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream);
+}
+
+int dfn_render_fwd_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                       const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                       const int32_t* pix_index, float* rgb_head, float* rgb_com, float* aux_head, float* aux_com, void* stream) {
+    if (!aux_head) return fail(DFN_E_ARG, "dfn_render_fwd_aux: aux_head is NULL");
+    if (frame && frame->fields == 2 && rgb_com && !aux_com)
+        return fail(DFN_E_ARG, "dfn_render_fwd_aux: aux_com missing for fields == 2");
+    const AuxOut aux = {aux_head, aux_com, nullptr, nullptr};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
+                           rgb_head, rgb_com, nullptr, nullptr, nullptr, 0, stream, &aux);
+}
+
+int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                          const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                          const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, uint8_t* alpha8_head,
+                          uint8_t* alpha8_com, uint16_t* depth16_head, uint16_t* depth16_com, void* stream) {
+    if (!alpha8_head && !depth16_head)
+        return fail(DFN_E_ARG, "dfn_render_fwd_u8_aux: neither alpha8_head nor depth16_head given (dfn_render_fwd_u8 is the call without aux outputs)");
+    if ((!alpha8_head && alpha8_com) || (!depth16_head && depth16_com))
+        return fail(DFN_E_ARG, "dfn_render_fwd_u8_aux: an output pair is selected by its _head pointer");
+    if (frame && frame->fields == 2 && rgb8_com && ((alpha8_head && !alpha8_com) || (depth16_head && !depth16_com)))
+        return fail(DFN_E_ARG, "dfn_render_fwd_u8_aux: alpha8_com / depth16_com missing for fields == 2");
+    const AuxOut aux = {alpha8_head, alpha8_com, depth16_head, depth16_com};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
+                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, &aux);
 }
 
 // ---- training ---------------------------------------------------------------------------------------------------
@@ -548,6 +592,7 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
     RenderArgs A;
     A.frame = F;
     A.out_u8 = 0;
+    A.aux = 0;
     A.wblob[0] = (const char*)packed_head;
     A.wblob[1] = (const char*)packed_torso;
     A.nslab[0] = ph.n_slabs;

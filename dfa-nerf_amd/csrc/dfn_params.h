@@ -16,13 +16,18 @@ struct RenderArgs {
     const int* pix_index;
     float* rgb_head;
     float* rgb_com;
-    float* w_head;
-    float* w_com;
-    float* z_out;
+    // the optional per-sample outputs - or, in an aux launch (`aux` below; the two are never combined, and the aux kernels write no
+    // per-sample output), the per-ray aux outputs in the same slots: the argument block, hence the kernel argument segment of every
+    // kernel, keeps its size and offsets
+    union { float* w_head; float* aux_head; unsigned char* alpha8_head; };      // aux: f32 [ray_count,2] {acc, depth}; u8 route: [ray_count]
+    union { float* w_com; float* aux_com; unsigned char* alpha8_com; };
+    union { float* z_out; unsigned short* depth16_head; };                      // aux, u8 route: [ray_count]
     int out_u8;                 // rgb_head / rgb_com point at uint8 [ray_count,3]: to8b in the epilogue (HELP:17)
+    int aux;                    // 1: launch the aux instantiation (render_kernel<TW | TIER_AUX>; inference only) - host-side dispatch only
     // training recorder (all null for inference): per-sample raw outputs and per-field activations / ReLU masks
     float* samples_out;         // [ray_count][n_coarse + n_fine][8], evaluation order (coarse points, then the fine ones)
-    unsigned char* ranks_out;   // hierarchical training: [ray_count][n_coarse + n_fine] merged rank of every evaluated point
+    // hierarchical training: [ray_count][n_coarse + n_fine] merged rank of every evaluated point (aux launch, u8 route: depth16_com)
+    union { unsigned char* ranks_out; unsigned short* depth16_com; };
     void* act_T[2];
     unsigned* masks[2];
     long NP;

@@ -1,0 +1,7 @@
+// dfn_render_f16_w128_aux.hip - the aux render kernels (TIER_AUX) of the 128-wide inference program (DFN_WIDTH_128) of the f16 tier
+// (templates: dfn_render_kernels.h, HT = 4)
+#include "dfn_render_kernels.h"
+
+namespace dfn {
+hipError_t launch_render_f16_w128_aux(const RenderArgs& A, hipStream_t st) { return launch_render_tier_aux<TIER_F16, TIER_W128>(A, st); }
+}  // namespace dfn

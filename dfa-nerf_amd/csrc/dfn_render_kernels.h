@@ -1,7 +1,8 @@
 // dfn_render_kernels.h - fused frame renderer and fused decoder for gfx950 (MI355X): the kernel templates.
 // Instantiated once per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip and, for the 128-wide inference program, in
-// dfn_render_{f32,f16,f16x3}_w128.hip (separate translation units: they build in parallel); dfn_render.hip dispatches on
-// the tier and the width.
+// dfn_render_{f32,f16,f16x3}_w128.hip; the instantiations that also write opacity and expected depth (TIER_AUX) in
+// dfn_render_{f32,f16,f16x3}[_w128]_aux.hip (separate translation units: they build in parallel); dfn_render.hip dispatches
+// on the tier, the width and the aux switch.
 //
 // One wavefront = one ray.  A workgroup of W waves (8 in the bf16 tier, 4 in the f32 tier) walks W rays
 // through: ray generation -> 64 coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
@@ -145,11 +146,21 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // tiles - dfn_mlp.h Prog<TIER, HT>).  Only the MLP passes differ between the widths: sampler, compositing, epilogues, LDS layout, ring,
 // workgroup shape and block mapping are the same code.  (The flag rides in the tier argument here as it does in the ABI: the 256-wide
 // kernels keep their template arguments, hence their names and their ISA.)
+// TIER_AUX in TW (inference only): the kernel also accumulates, per image, acc = sum over FG of w_i and depth = sum over FG of
+// mul_(w_i, z_i) of the FINAL pass (include/dfanerf.h, dfn_render_fwd_aux: FG = every sample but the background plane when
+// concate_bg) and writes them from the epilogue next to the RGB.  Order: per 32-sample tile each lane forms w and mul_(w, z)
+// (0.f outside FG), the 32 lanes combine by integrate_tile's butterfly (XOR 16, 8, 4, 2, 1), tiles add into the running sum in
+// tile order.  The running sums are wave-uniform and held in scalar registers (readfirstlane after the butterfly): no LDS, and
+// no vector register is live across an MLP pass for them.  The colour arithmetic is untouched: the RGB is the plain kernel's
+// bit for bit.  An aux launch writes no per-sample output (the argument slots of w_head / w_com / z_out carry the aux pointers,
+// dfn_params.h).
 template <int TW, bool TWO, int TRAIN, bool ACT4 = true>
 __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & TIER_MASK)>::THREADS / 256) void render_kernel(
     const RenderArgs A) {
     constexpr int TIER = TW & TIER_MASK, HT = (TW & TIER_W128) ? 4 : 8;
     static_assert(HT == 8 || TRAIN == 0, "the 128-wide program is inference only");
+    constexpr bool AUX = (TW & TIER_AUX) != 0;
+    static_assert(!AUX || TRAIN == 0, "the aux outputs are inference only");
     using C = TierCfg<TIER>;
     using L = KernelLds<TIER, TWO>;
     using P = Prog<TIER, HT>;
@@ -296,6 +307,20 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 #pragma unroll
         for (int k = 0; k < 3; ++k) fm[k] = add_(mul_(fh[k], wh), mul_(ft[k], wt));
     };
+    // AUX: running (acc, depth) of the head image and of the composite image, wave-uniform (scalar registers)
+    float acc_h = 0.f, dep_h = 0.f, acc_c = 0.f, dep_c = 0.f;
+    // one tile's share: w and mul_(w, z) of the lanes in FG, the colour sums' butterfly, then the running sums in tile order
+    auto aux_tile = [&](float& acc, float& dep, float w, float z, bool fg) {
+        float a = fg ? w : 0.f, d = fg ? mul_(w, z) : 0.f;
+#pragma unroll
+        for (int dlt = 16; dlt >= 1; dlt >>= 1) {
+            a += __shfl_xor(a, dlt, 32);
+            d += __shfl_xor(d, dlt, 32);
+        }
+        // (both half-waves hold the same 32 samples: the sums are the same in every lane)
+        acc = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(acc + a)));
+        dep = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dep + d)));
+    };
     // calc_volume_weights + colour sum over the S merged samples held in M (4 rows: sigma, r, g, b)
     auto composite_merged = [&](bool head_image, float* w_out) {
         for (int t = 0; t < S / 32; ++t) {
@@ -314,7 +339,10 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             } else {
                 w = integrate_tile(st, RS_TC, RS_RGB_C, sg, mul_(dz, st[RS_NT]), col, n, lane);
             }
-            if (valid && lane < 32) {
+            if constexpr (AUX) {
+                if (head_image) aux_tile(acc_h, dep_h, w, z, !(cbg && last));
+                else aux_tile(acc_c, dep_c, w, z, !(cbg && last));
+            } else if (valid && lane < 32) {
                 if (w_out) w_out[(size_t)r_raw * S + si] = w;
                 if (head_image && A.z_out) A.z_out[(size_t)r_raw * S + si] = z;
             }
@@ -401,9 +429,15 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
                 }
                 w_c = integrate_tile(st, RS_TC, RS_RGB_C, ssum, mul_(dz, st[RS_NT]), fm, n, lane);
             }
+            if constexpr (AUX) {             // coarse-only: this is the final pass (hierarchical: composite_merged sums)
+                if (!hier) {
+                    aux_tile(acc_h, dep_h, w_h, z, !(cbg && last));
+                    if (two) aux_tile(acc_c, dep_c, w_c, z, !(cbg && last));
+                }
+            }
             if (hier) {
                 if (lane < 32) tmp[si] = two ? w_c : w_h;
-            } else if (valid && lane < 32) {
+            } else if (!AUX && valid && lane < 32) {
                 if (A.w_head) A.w_head[(size_t)r_raw * NC + si] = w_h;
                 if (A.w_com && two) A.w_com[(size_t)r_raw * NC + si] = w_c;
                 if (A.z_out) A.z_out[(size_t)r_raw * NC + si] = z;
@@ -584,7 +618,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
         }
     }
 #ifdef DFN_TIMING
-    if (valid && lane == 0 && A.z_out) {
+    if (!AUX && valid && lane == 0 && A.z_out) {
         const unsigned long long T_end = __builtin_readcyclecounter();
         const unsigned long long R_end = __builtin_amdgcn_s_memrealtime();
         float* o = A.z_out + (size_t)r_raw * S + 64;
@@ -607,6 +641,29 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             for (int k = 0; k < 3; ++k) {
                 A.rgb_head[(size_t)r_raw * 3 + k] = st[RS_RGB_H + k];
                 if (two && A.rgb_com) A.rgb_com[(size_t)r_raw * 3 + k] = st[RS_RGB_C + k];
+            }
+        }
+    }
+    if constexpr (AUX) {
+        // dfn_render_fwd_aux: {acc, depth} per ray and image; dfn_render_fwd_u8_aux: alpha8 = to8b(acc), depth16 = 65535 *
+        // clip(depth / z_far, 0, 1) truncated (include/dfanerf.h), each pair of outputs optional
+        if (valid && lane == 0) {
+            if (A.out_u8) {
+                if (A.alpha8_head) A.alpha8_head[r_raw] = (unsigned char)(int)mul_(255.0f, fminf(fmaxf(acc_h, 0.f), 1.f));
+                if (A.depth16_head)
+                    A.depth16_head[r_raw] = (unsigned short)(int)mul_(65535.0f, fminf(fmaxf(div_(dep_h, F.z_far), 0.f), 1.f));
+                if (two) {
+                    if (A.alpha8_com) A.alpha8_com[r_raw] = (unsigned char)(int)mul_(255.0f, fminf(fmaxf(acc_c, 0.f), 1.f));
+                    if (A.depth16_com)
+                        A.depth16_com[r_raw] = (unsigned short)(int)mul_(65535.0f, fminf(fmaxf(div_(dep_c, F.z_far), 0.f), 1.f));
+                }
+            } else {
+                A.aux_head[(size_t)r_raw * 2 + 0] = acc_h;
+                A.aux_head[(size_t)r_raw * 2 + 1] = dep_h;
+                if (two && A.aux_com) {
+                    A.aux_com[(size_t)r_raw * 2 + 0] = acc_c;
+                    A.aux_com[(size_t)r_raw * 2 + 1] = dep_c;
+                }
             }
         }
     }
@@ -771,7 +828,7 @@ template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true, int W128 = 0> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
-    static_assert(W128 == 0 || (W128 == TIER_W128 && TRAIN == 0), "widths");
+    static_assert((W128 & ~(TIER_W128 | TIER_AUX)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux: inference only");      // (W128 also carries TIER_AUX)
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER, TWO>::TOTAL;
     static bool attr_done = false;
@@ -817,6 +874,12 @@ template <int TIER, bool TRAINABLE> static hipError_t launch_render_tier(const R
 template <int TIER> static hipError_t launch_render_tier_w128(const RenderArgs& A, hipStream_t st) {
     if (A.samples_out) return hipErrorInvalidValue;
     return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, TIER_W128>(A, st) : launch_render_t<TIER, false, 0, true, TIER_W128>(A, st);
+}
+// the aux instantiations of one tier and width (dfn_render_<tier>[_w128]_aux.hip; inference only: the API offers them in
+// dfn_render_fwd_aux / dfn_render_fwd_u8_aux alone)
+template <int TIER, int W128 = 0> static hipError_t launch_render_tier_aux(const RenderArgs& A, hipStream_t st) {
+    if (A.samples_out || !A.aux) return hipErrorInvalidValue;
+    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, W128 | TIER_AUX>(A, st) : launch_render_t<TIER, false, 0, true, W128 | TIER_AUX>(A, st);
 }
 template <int TIER> static hipError_t launch_decoder_tier_w128(const DecoderArgs& A, hipStream_t st) {
     if (A.act_T) return hipErrorInvalidValue;

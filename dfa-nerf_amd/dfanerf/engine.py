@@ -346,9 +346,16 @@ def make_frame(H, W, focal, cx, cy, pose, pose_body, near, far, last_dist=1e10, 
     return fr
 
 
-def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head=None, out_com=None, want_z=False):
+def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head=None, out_com=None, want_z=False,
+           want_aux=False):
     """dfn_render_fwd.  bg: f32 [H*W,3] in [0,1] or uint8 [H*W,3] device tensor.
-    Returns (rgb_head [n,3], rgb_com [n,3] or None[, w_head, w_com])."""
+    Returns (rgb_head [n,3], rgb_com [n,3] or None[, w_head, w_com][, z_vals][, aux_head, aux_com]).
+    want_aux: dfn_render_fwd_aux - aux_head / aux_com [n,2] = (acc, depth): opacity and premultiplied expected depth of each image
+    (include/dfanerf.h); aux_com is None with one field.  Not together with want_weights / want_z: the aux kernels write no
+    per-sample output (reduce the weights of a plain call instead)."""
+    if want_aux and (want_weights or want_z):
+        raise ValueError("render: want_aux cannot be combined with want_weights / want_z (dfn_render_fwd_aux has no per-sample "
+                         "outputs; call render() twice, or reduce the weights yourself)")
     dev = packed.device
     n = frame.ray_count
     two = frame.fields == 2
@@ -369,6 +376,14 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
     if pix_index is not None:
         pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
+    if want_aux:
+        aux_h = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        aux_c = torch.empty(n, 2, dtype=torch.float32, device=dev) if two else None
+        check(lib.dfn_render_fwd_aux(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+                                     _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
+                                     _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(aux_h),
+                                     _ptr(aux_c), _stream()), "dfn_render_fwd_aux")
+        return rgb_h, rgb_c, aux_h, aux_c
     check(lib.dfn_render_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
                              _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
                              _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h),
@@ -381,8 +396,11 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     return out
 
 
-def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=None):
-    """dfn_render_fwd_u8: the same launch with to8b fused into the epilogue -> uint8 [n,3] images (head, composite)."""
+def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=None, want_alpha=False, want_depth=False):
+    """dfn_render_fwd_u8: the same launch with to8b fused into the epilogue -> uint8 [n,3] images (head, composite).
+    want_alpha / want_depth: dfn_render_fwd_u8_aux - the return value grows by (alpha8_head, alpha8_com) uint8 [n] and / or
+    (depth16_head, depth16_com) uint16 [n], in this order (the _com entries None with one field); include/dfanerf.h has the
+    formulas.  Without them the plain entry point is the one called."""
     dev = packed.device
     n = frame.ray_count
     two = frame.fields == 2
@@ -399,6 +417,21 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
     bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
     if pix_index is not None:
         pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
+    if want_alpha or want_depth:
+        a_h = torch.empty(n, dtype=torch.uint8, device=dev) if want_alpha else None
+        a_c = torch.empty(n, dtype=torch.uint8, device=dev) if (want_alpha and two) else None
+        d_h = torch.empty(n, dtype=torch.uint16, device=dev) if want_depth else None
+        d_c = torch.empty(n, dtype=torch.uint16, device=dev) if (want_depth and two) else None
+        check(lib.dfn_render_fwd_u8_aux(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+                                        _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
+                                        _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _ptr(a_h), _ptr(a_c),
+                                        _ptr(d_h), _ptr(d_c), _stream()), "dfn_render_fwd_u8_aux")
+        out = (out_h, out_c)
+        if want_alpha:
+            out += (a_h, a_c)
+        if want_depth:
+            out += (d_h, d_c)
+        return out
     check(lib.dfn_render_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
                                 _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
                                 _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()),

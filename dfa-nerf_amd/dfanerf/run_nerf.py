@@ -37,11 +37,22 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 # ------------------------------------------------------------------------------------------------------------
 class ConfigArgParser(argparse.ArgumentParser):
     """argparse + `--config file` of `key = value` lines (what configargparse gives the reference):
-    file values act as defaults, explicit command-line flags win."""
+    file values act as defaults, explicit command-line flags win.
+    side: an optional second parser of store_true switches (config_parser: _OUTPUT_FLAGS); its flags are taken off the command
+    line first and land in the same namespace."""
+    side = None
+
+    def format_help(self):
+        return super().format_help() + ("\n" + self.side.format_help() if self.side is not None else "")
 
     def parse_args(self, args=None, namespace=None):
         import sys
         argv = list(sys.argv[1:] if args is None else args)
+        if self.side is not None:
+            side_ns, argv = self.side.parse_known_args(argv)
+            namespace = namespace if namespace is not None else argparse.Namespace()
+            for k, v in vars(side_ns).items():
+                setattr(namespace, k, v)
         pre = argparse.ArgumentParser(add_help=False)
         pre.add_argument('--config')
         known, _ = pre.parse_known_args(argv)
@@ -102,8 +113,13 @@ _FLAGS = [
 # --hip_train_act: format of the activations the 16-bit training step records for its weight gradients (fp4 | e4m3)
 # --hip_f16_model_psnr: the model's PSNR against ground truth, for the f16 tier's accuracy guard where the frames being rendered
 # have no ground truth (f16guard.py)
+# --save_alpha / --save_depth: next to every rendered frame its opacity (alpha matte) and its expected depth, from the same launch
+# (dfn_render_fwd_u8_aux)
 _EXTRA_FLAGS = [("hip_tier", str, 'f32'), ("hierarchical", None, None), ("image_ext", str, 'jpg'), ("hip_train_act", str, 'fp4'),
                 ("hip_f16_model_psnr", float, 30.0)]
+# switches of what the render paths WRITE next to the frames (store_true; help in the table below).  They are parsed by a side
+# parser (ConfigArgParser.side): the flag table proper stays the reference's flags plus the build-side switches above
+_OUTPUT_FLAGS = ("save_alpha", "save_depth")
 _EXTRA_HELP = {
     "hip_tier": "precision tier of the HIP path: f32 (exact MFMA products, the parity tier; default) | f16 (throughput tier "
                 "for rendering: f16 MFMA operands, f32 accumulation) | f16x3 (rendering with the f32 tier's accuracy at about 3x "
@@ -122,6 +138,13 @@ _EXTRA_HELP = {
                      "tests/test_gpu_convergence.py trains to convergence in both) | e4m3 (MX-fp8, +5 % step time)",
     "hierarchical": "64 + N_importance samples per ray (coarse pass -> sample_pdf -> the same decoder on the merged depths)",
     "image_ext": "file type of the rendered frames (jpg as upstream; png keeps the kernel's uint8 output losslessly)",
+    "save_alpha": "write, next to every rendered frame <name>.<ext>, <name>_alpha.png: the opacity of the rendered foreground (alpha "
+                  "matte of the head in render_head/, of head + torso in render_com/; background plane excluded) as 8-bit greyscale, "
+                  "255 * acc truncated.  Always PNG.  --render_person and --render_final_video; the in-training preview ignores it; "
+                  "one rank only (the per-frame gather carries RGB); tiers f32 / f16 / f16x3",
+    "save_depth": "write <name>_depth.png next to every rendered frame: the expected depth of the foreground, PREMULTIPLIED by the "
+                  "opacity (sum of weight * z over the foreground samples; divide by alpha for a mean depth), as 16-bit greyscale "
+                  "(PIL mode I;16), 65535 * depth / far truncated.  Otherwise as --save_alpha",
 }
 
 
@@ -136,6 +159,10 @@ def config_parser():
             parser.add_argument('--' + name, action='store_false', **kw)
         else:
             parser.add_argument('--' + name, type=typ, default=default, **kw)
+    parser.side = argparse.ArgumentParser(add_help=False, allow_abbrev=False, usage=argparse.SUPPRESS)
+    grp = parser.side.add_argument_group("what the render paths write next to every frame (this build)")
+    for name in _OUTPUT_FLAGS:
+        grp.add_argument('--' + name, action='store_true', help=_EXTRA_HELP[name])
     return parser
 
 
@@ -256,6 +283,7 @@ class _FrameWriter:
         self.ring = [[torch.empty(H, W, 3, dtype=torch.uint8, pin_memory=self.cuda) for _ in range(n_images)]
                      for _ in range(depth)]
         self.pending = [None] * depth
+        self.xring = {}                                      # slot -> pinned buffers of the extra planes (submit)
         self.k = 0
         self._kept = {}
         self._keep_list = None
@@ -273,8 +301,10 @@ class _FrameWriter:
                 self._keep_list.append(a)
             self._flushed += 1
 
-    def submit(self, images, paths, keep=None):
-        """images: uint8 device tensors [H,W,3]; paths: file per image (None = do not write)."""
+    def submit(self, images, paths, keep=None, extras=()):
+        """images: uint8 device tensors [H,W,3]; paths: file per image (None = do not write).
+        extras: (device tensor [H,W] uint8 / uint16, path) pairs written as greyscale PNG by the same worker (--save_alpha /
+        --save_depth); their pinned buffers join the slot's ring on first use."""
         if self.t0 is None:
             self.t0 = self._time()
         slot = self.k % len(self.ring)
@@ -293,6 +323,12 @@ class _FrameWriter:
         bufs = self.ring[slot]
         for b, img in zip(bufs, images):
             b.copy_(img, non_blocking=True)
+        extras = [(t, pth) for t, pth in extras if t is not None and pth]
+        xb = self.xring.setdefault(slot, [])
+        for i, (t, _) in enumerate(extras):
+            if i >= len(xb) or xb[i].dtype != t.dtype or xb[i].shape != t.shape:
+                xb[i:i + 1] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=self.cuda)]
+            xb[i].copy_(t, non_blocking=True)
         ev = None
         if self.cuda:
             ev = torch.cuda.Event()
@@ -306,6 +342,8 @@ class _FrameWriter:
             for a, pth in zip(arrs, paths):
                 if pth:
                     _imwrite(pth, a)
+            for b, (_, pth) in zip(xb, extras):
+                _imwrite_gray(pth, b.numpy())
             dt = self._time() - t
             with self._lock:
                 # a marker per frame only while a keep list is active (it keeps the sequence gap-free for _flush_kept);
@@ -338,6 +376,10 @@ class _FrameWriter:
                 "submit_waited_s": self.blocked_s}
 
 
+_AUX_RANKS_MSG = ("--save_alpha / --save_depth need a single rank: the per-frame gather across the ranks carries the RGB images only "
+                  "(widening it is not implemented); render with one process, or drop the flags")
+
+
 class FrameRenderer:
     """Replaces the chunked frame loop (MAIN:633-715): one fused launch per frame (per rank)."""
 
@@ -359,6 +401,8 @@ class FrameRenderer:
         self.zs = z_shape[0, 2 * itr_obj:2 * itr_obj + 2].to(dev).float().contiguous()
         self.za = z_app[0, 2 * itr_obj:2 * itr_obj + 2].to(dev).float().contiguous()
         self.n_fine = args.N_importance if getattr(args, "hierarchical", False) else 0
+        # --save_alpha / --save_depth: what render_image_begin(aux=True) asks the kernel for next to the uint8 images
+        self.save_alpha, self.save_depth = bool(getattr(args, "save_alpha", False)), bool(getattr(args, "save_depth", False))
 
     @property
     def guarded(self):
@@ -460,10 +504,11 @@ class FrameRenderer:
         return self.tier
 
     def render(self, pose, pose_body, signal, signal_torso, ray_begin=0, ray_count=None, pix_index=None, fields=2,
-               out_u8=False, out=None, bias=None):
+               out_u8=False, out=None, bias=None, want_alpha=False, want_depth=False):
         """-> rgb_head [n,3], rgb_com [n,3] (None if fields == 1); out_u8: uint8 images, to8b fused into the kernel;
         out: (head, com) tensors the kernel writes into (e.g. slices of the shard that is gathered); bias: the frame's folded
-        bias blob if the caller already has it (engine.FramePrefetcher), instead of the two signals."""
+        bias blob if the caller already has it (engine.FramePrefetcher), instead of the two signals.
+        want_alpha / want_depth (with out_u8): engine.render_u8's extra outputs follow, in its order."""
         eng = self.engine
         pk = self.decoder.packed(self.tier)
         if bias is None:
@@ -476,20 +521,38 @@ class FrameRenderer:
                             self.far, self.args.last_dist, ray_begin, n, self.args.N_samples, self.n_fine, fields,
                             self.args.concate_bg)
         oh, oc = out if out is not None else (None, None)
+        if (want_alpha or want_depth) and not out_u8:
+            raise ValueError("FrameRenderer.render: want_alpha / want_depth belong to the uint8 route (out_u8=True); "
+                             "engine.render(want_aux=True) returns the float values")
         if out_u8:
-            return eng.render_u8(pk, bias, fr, self.bg, pix_index=pix_index, out_head=oh, out_com=oc)
+            return eng.render_u8(pk, bias, fr, self.bg, pix_index=pix_index, out_head=oh, out_com=oc, want_alpha=want_alpha,
+                                 want_depth=want_depth)
         return eng.render(pk, bias, fr, self.bg, pix_index=pix_index, out_head=oh, out_com=oc)
 
-    def render_image_begin(self, pose, pose_body, signal, signal_torso, fields=2, out_u8=False, bias=None):
+    def render_image_begin(self, pose, pose_body, signal, signal_torso, fields=2, out_u8=False, bias=None, aux=False):
         """Start a whole frame: render this rank's ray shard and ISSUE the gather (async_op=True: it runs on the backend's
         own stream) -> a handle for render_image_end().  Two sets of shard / gather buffers alternate, so the gather of
         frame k runs underneath the render of frame k + 1: call begin(k + 1) before end(k).  ONE
-        collective per frame: the kernel writes both images into one padded [n_img, per, 3] shard."""
+        collective per frame: the kernel writes both images into one padded [n_img, per, 3] shard.
+        aux: also what --save_alpha / --save_depth select (render_image_aux(handle) returns it); one rank only - the gather
+        carries RGB."""
         import torch.distributed as dist
         R = self.H * self.W
+        aux = bool(aux) and (self.save_alpha or self.save_depth)
         if not (dist.is_initialized() and dist.get_world_size() > 1):
+            if aux:
+                res = self.render(pose, pose_body, signal, signal_torso, fields=fields, out_u8=out_u8, bias=bias,
+                                  want_alpha=self.save_alpha, want_depth=self.save_depth)
+                planes = {}
+                if self.save_alpha:
+                    planes["alpha_head"], planes["alpha_com"] = res[2:4]
+                if self.save_depth:
+                    planes["depth_head"], planes["depth_com"] = res[-2:]
+                return {"images": res[:2], "aux": planes}
             rh, rc = self.render(pose, pose_body, signal, signal_torso, fields=fields, out_u8=out_u8, bias=bias)
             return {"images": (rh, rc)}
+        if aux:
+            raise RuntimeError(_AUX_RANKS_MSG)
         world = dist.get_world_size()
         begin, count, per = parallel.shard_range(R, world, dist.get_rank())
         n_img = 2 if fields == 2 else 1
@@ -539,6 +602,11 @@ class FrameRenderer:
             g = slot["gathered"].permute(1, 0, 2, 3).reshape(h["n_img"], h["world"] * h["per"], 3)[:, :R]
             rh, rc = g[0], (g[1] if h["fields"] == 2 else None)
         return rh.reshape(self.H, self.W, 3), (rc.reshape(self.H, self.W, 3) if rc is not None else None)
+
+    def render_image_aux(self, h):
+        """The aux planes of a frame started with render_image_begin(aux=True): {"alpha_head", "alpha_com"} uint8 [H,W] and /
+        or {"depth_head", "depth_com"} uint16 [H,W] (the _com entries None with one field); {} when none were asked for."""
+        return {k: (v.reshape(self.H, self.W) if v is not None else None) for k, v in h.get("aux", {}).items()}
 
     def render_image(self, pose, pose_body, signal, signal_torso, fields=2, out_u8=False):
         """Whole frame, sharded over the ranks when torch.distributed is initialised -> [H,W,3] images
@@ -628,6 +696,16 @@ def _imread(path):
 def _imwrite(path, arr):
     from PIL import Image
     Image.fromarray(np.asarray(arr, np.uint8)).save(path, quality=95)
+
+
+def _imwrite_gray(path, arr):
+    """[H,W] uint8 -> 8-bit greyscale PNG (mode L); uint16 -> 16-bit greyscale PNG (mode I;16)"""
+    from PIL import Image
+    a = np.ascontiguousarray(arr)
+    if a.dtype == np.uint16:
+        Image.frombytes('I;16', (a.shape[1], a.shape[0]), a.astype('<u2').tobytes()).save(path, format='PNG')
+    else:
+        Image.frombytes('L', (a.shape[1], a.shape[0]), a.astype(np.uint8).tobytes()).save(path, format='PNG')
 
 
 def _mimwrite(path, frames, fps=25):
@@ -832,6 +910,8 @@ def check_supported(args):
         bad.append(f"--hip_tier {args.hip_tier} (f32 | f16 | f16x3 | bf16 | auto)")
     if getattr(args, "hip_train_act", "fp4") not in ("fp4", "e4m3"):
         bad.append(f"--hip_train_act {args.hip_train_act} (fp4 | e4m3)")
+    if (getattr(args, "save_alpha", False) or getattr(args, "save_depth", False)) and args.hip_tier == "bf16":
+        bad.append("--save_alpha / --save_depth with --hip_tier bf16 (the opacity / depth outputs exist in the f32, f16 and f16x3 tiers)")
     if bad:
         raise SystemExit("run_nerf_com_trainExpLater.py (MI355X build): unsupported configuration:\n  " + "\n  ".join(bad))
 
@@ -841,6 +921,9 @@ def train():
     args = config_parser().parse_args()
     check_supported(args)
     world, rank, local = parallel.init()
+    want_aux = bool(getattr(args, "save_alpha", False) or getattr(args, "save_depth", False))
+    if want_aux and world > 1:
+        raise SystemExit("run_nerf_com_trainExpLater.py (MI355X build): " + _AUX_RANKS_MSG)
     dev = torch.device("cuda", local) if torch.cuda.is_available() else torch.device("cpu")
     if dev.type != "cuda":
         raise RuntimeError("train(): no HIP device visible; the render path has no CPU fallback")
@@ -920,9 +1003,14 @@ def train():
         def finish(handle, img_i):
             rgb8_head, rgb8 = renderer.render_image_end(handle)
             if rank == 0:
+                # --save_alpha / --save_depth: <name>_alpha.png / <name>_depth.png next to each image's file
+                planes = renderer.render_image_aux(handle)
+                stem = os.path.splitext(tag.format(img_i))[0]
+                extras = [(planes.get(kind + "_" + img), os.path.join(d, stem + "_" + kind + ".png") if d else None)
+                          for kind in ("alpha", "depth") for img, d in (("com", outdir_com), ("head", outdir_head))]
                 writer.submit([rgb8, rgb8_head],
                               [os.path.join(outdir_com, tag.format(img_i)),
-                               os.path.join(outdir_head, tag.format(img_i)) if outdir_head else None], keep=rgbs)
+                               os.path.join(outdir_head, tag.format(img_i)) if outdir_head else None], keep=rgbs, extras=extras)
                 print('Saved test img at {}'.format(os.path.join(outdir_com, tag.format(img_i))))
         pending = None
         frame_ids = list(frame_ids)
@@ -957,7 +1045,8 @@ def train():
             with torch.no_grad():
                 if pf is not None:
                     bias = pf.get(img_i, frame_ids[k + 1] if k + 1 < len(frame_ids) else None)
-                    handle = renderer.render_image_begin(poses_host[img_i], body_host, None, None, out_u8=True, bias=bias)
+                    handle = renderer.render_image_begin(poses_host[img_i], body_host, None, None, out_u8=True, bias=bias,
+                                                         aux=want_aux)
                     with torch.cuda.stream(handle.get("stream") or torch.cuda.current_stream(dev)):
                         pf.done()                       # (on the stream the render that read the blob runs on)
                     if pending is not None:
@@ -971,7 +1060,7 @@ def train():
                                                        args, len_sig, embed_fn=embed_fn)
                 # uint8 straight from the kernel epilogue (to8b fused), gathered as uint8 across the ranks; pipelined by one
                 # frame: this frame's render is enqueued BEFORE the previous frame's gather is waited for
-                handle = renderer.render_image_begin(poses_host[img_i], body_host, signal, signal_torso, out_u8=True)
+                handle = renderer.render_image_begin(poses_host[img_i], body_host, signal, signal_torso, out_u8=True, aux=want_aux)
                 if pending is not None:
                     finish(*pending)
                 pending = (handle, img_i)
@@ -999,6 +1088,9 @@ def train():
             _mimwrite(os.path.join(out_com, '{}.mp4'.format(args.expname)), rgbs)
         return
 
+    if want_aux and rank == 0:
+        print("[dfanerf] --save_alpha / --save_depth: written for the rendered frames (--render_person, --render_final_video); the "
+              "in-training preview ignores them")
     from . import training
     # the 16-bit training tier is bf16 (f16, the inference throughput tier, has too little exponent range for gradients)
     tier = getattr(args, "hip_tier", "f32")

@@ -47,7 +47,7 @@ extern "C" {
  * <= 128: 4 output tiles per trunk layer and half-length K over the hidden vector, 314 instead of 1,138 MFMA fragments per head
  * pass (16-bit tiers; torso 450 instead of 1,306).
  *   - accepted with DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 by dfn_packed_bytes, dfn_pack_weights, dfn_pack_plan, dfn_render_fwd,
- *     dfn_render_fwd_u8 and dfn_decoder_fwd; dfn_bias_floats and dfn_fold_bias accept and ignore it (the bias blob keeps its layout
+ *     dfn_render_fwd_u8 (and their _aux forms) and dfn_decoder_fwd; dfn_bias_floats and dfn_fold_bias accept and ignore it (the bias blob keeps its layout
  *     and its 256-float strides: the narrow kernels read the first 128 entries of each hidden-sized vector);
  *   - with DFN_TIER_BF16 (the training tier: it stays padded) and in every other entry point that takes a tier - the training
  *     forwards, the backward streams and kernels, the gradient calls - the result is DFN_E_ARG, before any device work;
@@ -66,7 +66,8 @@ extern "C" {
 #define DFN_N_DECODER_PARAMS 955242
 
 const char* dfn_last_error(void);
-/* library build info: "dfanerf <version> gfx950".  ABI notes - DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+/* library build info: "dfanerf <version> gfx950".  ABI notes - 0.4: + dfn_render_fwd_aux, dfn_render_fwd_u8_aux (per-ray opacity and
+ * expected depth next to the RGB; inference tiers, both widths; nothing else changes).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -171,6 +172,42 @@ int dfn_render_fwd(int tier, const DfnFrame* frame, const void* packed_head, con
 int dfn_render_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                       const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                       const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream);
+
+/* dfn_render_fwd with two more per-ray results per image: the OPACITY of the rendered foreground (the alpha matte of the head, or
+ * of head + torso) and the EXPECTED DEPTH.  Extends dfn_render_fwd (MAIN:611-713): the weights are calc_volume_weights' (MAIN:169-179,
+ * 706-709), reduced in the kernel instead of being returned as [ray_count, S] arrays.  One ray, one image (the head image uses the
+ * head's weights, the composite image the two-field weights), FINAL pass - the merged S = n_coarse + n_fine samples when
+ * n_fine > 0, otherwise the S = n_coarse coarse samples:
+ *   FG     with concate_bg != 0: every sample except the last in depth order (index S - 1) - that one is the background plane (its
+ *          colour is the plate, MAIN:669-671, its sigma gets the 1e-6 bump, its weight is the ray's remaining transmittance);
+ *          with concate_bg == 0: all samples
+ *   acc    = sum over FG of w_i                    opacity, in [0, 1]
+ *   depth  = sum over FG of w_i * z_i              expected depth, PREMULTIPLIED: it is NOT divided by acc (depth / acc is the
+ *          mean depth of the foreground; the caller divides).  In the units of z_near / z_far (z_i is the sample's z_vals entry):
+ *          multiply by the ray norm |d| for a metric distance along the ray.  depth <= acc * z_far.
+ * Summation order (fixed): per 32-sample tile each lane forms w and the rounded product w * z (0.f outside FG); the 32 lanes
+ * combine by a butterfly at XOR distances 16, 8, 4, 2, 1, as the colour sums do; the tiles' sums add into a running sum in tile
+ * order; plain f32 additions.
+ *   aux_head [ray_count,2] = {acc, depth} of the head image (required)
+ *   aux_com  [ray_count,2] of the composite image: required when fields == 2 (i.e. when rgb_com is), NULL when fields == 1
+ * rgb_head / rgb_com are dfn_render_fwd's bit for bit.  No weights_* / z_vals outputs in this form.  Tiers DFN_TIER_F32 /
+ * DFN_TIER_F16 / DFN_TIER_F16X3, with or without DFN_WIDTH_128; DFN_TIER_BF16 (the training tier) gives DFN_E_ARG before any device
+ * work, and no training entry point has an aux form.  Other argument checks: dfn_render_fwd's. */
+int dfn_render_fwd_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                       const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                       const int32_t* pix_index, float* rgb_head, float* rgb_com, float* aux_head, float* aux_com, void* stream);
+
+/* dfn_render_fwd_u8 with the aux results of dfn_render_fwd_aux converted in the kernel epilogue (extends the fused output stage,
+ * SURVEY.md 8(f) rank 1; same exact-rounding f32 arithmetic as to8b, HELP:17):
+ *   alpha8  [ray_count] uint8  = (uint8)(int)(255 * clip(acc, 0, 1))                     i.e. to8b(acc)
+ *   depth16 [ray_count] uint16 = (uint16)(int)(65535 * clip(depth / z_far, 0, 1))        (depth <= acc * z_far: the quotient is in [0, 1])
+ * each product and the quotient rounded to f32 once, then truncated.  Each PAIR (alpha8_*, depth16_*) is optional and selected by
+ * its _head pointer; at least one must be given.  A selected pair needs its _com pointer when fields == 2 (NULL when fields == 1).
+ * rgb8_* are dfn_render_fwd_u8's bit for bit.  Tiers and refusals as dfn_render_fwd_aux. */
+int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                          const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                          const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, uint8_t* alpha8_head,
+                          uint8_t* alpha8_com, uint16_t* depth16_head, uint16_t* depth16_com, void* stream);
 
 /* ---- training step: replaces loss.backward() through MAIN:855-899 + DEC:277-349 (torch autograd upstream) ------
  * One step = dfn_train_fwd (the fused renderer with its recorder on: coarse samples, both fields) ->
