@@ -27,7 +27,7 @@ mkdir -p "$OBJ"
 # memory) and with the MX-fp8 recorder some bodies exceed LLVM's default budget of 16384 instructions
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-inline-asm -mllvm -pragma-unroll-threshold=200000 -I$SRC -I$HERE/../include $DFN_EXTRA_FLAGS"
 HDR_HASH="$( (cat "$SRC"/*.h "$HERE"/../include/*.h; echo "$FLAGS" | sed "s#$HERE#.#g"; hipcc --version 2>/dev/null | head -2) | sha256sum | cut -d' ' -f1)"
-UNITS="dfn_render dfn_render_f32 dfn_render_bf16 dfn_render_bf16e dfn_render_f16 dfn_render_f16x3 dfn_render_f32_w128 dfn_render_f16_w128 dfn_render_f16x3_w128 dfn_render_f32_aux dfn_render_f16_aux dfn_render_f16x3_aux dfn_render_f32_w128_aux dfn_render_f16_w128_aux dfn_render_f16x3_w128_aux dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
+UNITS="dfn_render dfn_render_f32 dfn_render_bf16 dfn_render_bf16e dfn_render_f16 dfn_render_f16x3 dfn_render_f32_w128 dfn_render_f16_w128 dfn_render_f16x3_w128 dfn_render_f32_aux dfn_render_f16_aux dfn_render_f16x3_aux dfn_render_f32_w128_aux dfn_render_f16_w128_aux dfn_render_f16x3_w128_aux dfn_render_f32_rays dfn_render_f16_rays dfn_render_f16x3_rays dfn_render_f32_w128_rays dfn_render_f16_w128_rays dfn_render_f16x3_w128_rays dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
 # the library's own stamp (next to the .so: it travels with it to the GPU box, the object directory does not): everything it
 # is made from, hashed - an up-to-date library is not rebuilt
 LIB_HASH="$( (echo "$HDR_HASH"; cat "$SRC"/*.hip "$SRC"/*.cpp) | sha256sum | cut -d' ' -f1)"
@@ -48,8 +48,9 @@ g++ -O2 -std=c++17 -fPIC -I"$SRC" -I"$HERE/../include" -c "$SRC/dfn_plan.cpp" -o
 for p in "${pids[@]}"; do wait $p; done
 # the asm fragment fetch (DFN_ASM_FETCH) is only safe if nothing touches an in-flight destination register
 # (f16x3: compiler-scheduled fragment reads, checked all the same)
-# (_w128: the 128-wide inference program of the same tier, same rules; _aux: the kernels that also write opacity and depth, same rules)
-for t in bf16 bf16e f16 f16x3 f16_w128 f16x3_w128 f16_aux f16x3_aux f16_w128_aux f16x3_w128_aux; do
+# (_w128: the 128-wide inference program of the same tier, same rules; _aux: the kernels that also write opacity and depth, same rules;
+# _rays: the kernels for caller-supplied rays, same rules)
+for t in bf16 bf16e f16 f16x3 f16_w128 f16x3_w128 f16_aux f16x3_aux f16_w128_aux f16x3_w128_aux f16_rays f16x3_rays f16_w128_rays f16x3_w128_rays; do
   ISA="$OBJ/dfn_render_$t-hip-amdgcn-amd-amdhsa-gfx950.s"
   if [ -f "$ISA" ]; then
     python3 "$HERE/../tools/check_inflight.py" "$ISA" || { echo "build.sh: in-flight register hazard in the $t render kernels" >&2; exit 1; }

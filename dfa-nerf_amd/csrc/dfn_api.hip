@@ -350,13 +350,22 @@ int dfn_adam_multi(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int 
 struct AuxOut {
     void *head, *com, *d16_head, *d16_com;
 };
+// the per-ray inputs of a rays launch (dfn_render_rays_fwd[_u8]): rays f32 [ray_count, 6 * fields], bounds f32 [ray_count,2] or NULL
+struct RaysIn {
+    const float *rays, *bounds;
+};
 static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                            const float* bias_head, const float* bias_torso, const float* bg_f32,
                            const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
                            float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream,
-                           const AuxOut* aux = nullptr) {
+                           const AuxOut* aux = nullptr, const RaysIn* rin = nullptr) {
     int width;
     if (take_width(tier, width, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
+    // caller-supplied rays: the kernels exist in the inference tiers only, and without an aux form
+    if (rin && (tier == DFN_TIER_BF16 || aux))
+        return fail(DFN_E_ARG, "dfn_render_rays_fwd: caller-supplied rays exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
+                               "(bf16 is the training tier)");
+    if (rin && !rin->rays) return fail(DFN_E_ARG, "dfn_render_rays_fwd: rays is NULL (dfn_render_fwd renders the frame's own pinhole rays)");
     // the aux kernels exist in the inference tiers only (bf16 is the training tier)
     if (aux && tier == DFN_TIER_BF16)
         return fail(DFN_E_ARG, "dfn_render_fwd_aux: opacity / depth outputs exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
@@ -374,7 +383,8 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
         return fail(DFN_E_ARG, "dfn_render_fwd: torso inputs / rgb_com missing for fields == 2");
     if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, "dfn_render_fwd: no background given");
     if (F.ray_count <= 0) return DFN_OK;
-    if (F.H <= 0 || F.W <= 0 || (!pix_index && (F.ray_begin < 0 || F.ray_begin + F.ray_count > F.H * F.W)))
+    // (supplied rays: H, W, ray_begin, the intrinsics and the poses are ignored)
+    if (!rin && (F.H <= 0 || F.W <= 0 || (!pix_index && (F.ray_begin < 0 || F.ray_begin + F.ray_count > F.H * F.W))))
         return fail(DFN_E_ARG, "dfn_render_fwd: ray range outside the image");
     // the kernel reads [head | torso] biases from one LDS image: they must be adjacent in memory
     ProgramInfo ph, pt;
@@ -412,6 +422,12 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
     A.masks[0] = A.masks[1] = nullptr;
     A.NP = 0;
     A.act_e4m3 = 0;
+    A.use_rays = 0;
+    if (rin) {       // the rays kernels read no pixel id and record nothing: those argument slots carry the rays and the bounds (dfn_params.h)
+        A.use_rays = 1;
+        A.rays = rin->rays;
+        A.bounds = rin->bounds;
+    }
     A.loss = DfnTrainLoss{};
     A.clock_probe = g_clock_probe;
     hipError_t err = launch_render(tier, A, (hipStream_t)stream, width);
@@ -458,6 +474,23 @@ int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_he
     const AuxOut aux = {alpha8_head, alpha8_com, depth16_head, depth16_com};
     return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
                            (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, &aux);
+}
+
+int dfn_render_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                        const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                        const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* weights_head,
+                        float* weights_com, float* z_vals, void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head,
+                           rgb_com, weights_head, weights_com, z_vals, 0, stream, nullptr, &rin);
+}
+
+int dfn_render_rays_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                           const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                           const float* bg_f32, const uint8_t* bg_u8, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr,
+                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, nullptr, &rin);
 }
 
 // ---- training ---------------------------------------------------------------------------------------------------
@@ -593,6 +626,7 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
     A.frame = F;
     A.out_u8 = 0;
     A.aux = 0;
+    A.use_rays = 0;
     A.wblob[0] = (const char*)packed_head;
     A.wblob[1] = (const char*)packed_torso;
     A.nslab[0] = ph.n_slabs;

@@ -40,6 +40,9 @@ constexpr int TIER_W128 = 0x200, TIER_MASK = 0xff;
 // internal (no ABI flag: dfn_render_fwd_aux / dfn_render_fwd_u8_aux are entry points of their own), or'ed into the render kernel's
 // first template argument the same way: the instantiation that also writes the opacity and the expected depth of every image
 constexpr int TIER_AUX = 0x400;
+// internal, the same way (dfn_render_rays_fwd / dfn_render_rays_fwd_u8 are entry points of their own): the instantiation that reads
+// its rays - origins, directions, optionally per-ray (near, far) - from memory instead of generating pinhole rays.  Never with TIER_AUX
+constexpr int TIER_RAYS = 0x800;
 DFN_HD constexpr bool tier_is16(int tier) { return tier == TIER_BF16 || tier == TIER_F16; }     // 16-bit operand arithmetic
 DFN_HD constexpr bool tier_frag16(int tier) { return tier != TIER_F32; }                       // 16-bit fragment map (E = 8)
 DFN_HD constexpr int tier_split(int tier) { return tier == TIER_F16X3 ? 2 : 1; }                // fragments per k-unit and tile

@@ -1,5 +1,6 @@
 // dfn_params.h - kernel argument blocks (internal; the public structs live in include/dfanerf.h)
 #pragma once
+#include <cstddef>
 #include <hip/hip_runtime.h>
 #include "dfanerf.h"
 #include "dfn_layout.h"
@@ -13,7 +14,9 @@ struct RenderArgs {
     const float* bias;          // [head blob | torso blob], global
     const float* bg_f32;
     const unsigned char* bg_u8;
-    const int* pix_index;
+    // pixel ids of the rays - or, in a rays launch (`use_rays` below: the kernel generates no ray and reads no pixel id), the rays
+    // themselves in the same slot: f32 [ray_count, 6 * fields] = o_head[3], d_head[3][, o_torso[3], d_torso[3]]
+    union { const int* pix_index; const float* rays; };
     float* rgb_head;
     float* rgb_com;
     // the optional per-sample outputs - or, in an aux launch (`aux` below; the two are never combined, and the aux kernels write no
@@ -25,19 +28,24 @@ struct RenderArgs {
     int out_u8;                 // rgb_head / rgb_com point at uint8 [ray_count,3]: to8b in the epilogue (HELP:17)
     int aux;                    // 1: launch the aux instantiation (render_kernel<TW | TIER_AUX>; inference only) - host-side dispatch only
     // training recorder (all null for inference): per-sample raw outputs and per-field activations / ReLU masks
-    float* samples_out;         // [ray_count][n_coarse + n_fine][8], evaluation order (coarse points, then the fine ones)
+    // (rays launch - inference, so the recorder is off: `bounds`, optional f32 [ray_count,2] = (near, far) per ray; NULL = frame.z_near / z_far)
+    union { float* samples_out; const float* bounds; };         // [ray_count][n_coarse + n_fine][8], evaluation order (coarse points, then the fine ones)
     // hierarchical training: [ray_count][n_coarse + n_fine] merged rank of every evaluated point (aux launch, u8 route: depth16_com)
     union { unsigned char* ranks_out; unsigned short* depth16_com; };
     void* act_T[2];
     unsigned* masks[2];
     long NP;
     int act_e4m3;               // 16-bit training forward: act_T as MX-fp8 e4m3 instead of MX-fp4 (DFN_TRAIN_ACT_E4M3)
+    int use_rays;               // 1: launch the rays instantiation (render_kernel<TW | TIER_RAYS>; inference only) - host-side dispatch only
+                                // (sits in the padding in front of `loss`: the argument block keeps its size and offsets)
     // training forward with the loss in its epilogue (dfn_train_fwd_loss; losses == null: off)
     DfnTrainLoss loss;
     // debug (dfn_debug_clock_probe): the workgroup in the middle of the grid writes {shader cycles, 100 MHz ticks} of its
     // own lifetime -> the effective shader clock UNDER LOAD of this launch.  Null = off.
     unsigned long long* clock_probe;
 };
+
+static_assert(offsetof(RenderArgs, loss) == offsetof(RenderArgs, act_e4m3) + 8, "use_rays must sit in the padding in front of loss");
 
 struct DecoderArgs {
     const char* wblob;

@@ -1,7 +1,8 @@
 // dfn_render.hip - tier and width dispatch of the fused frame renderer and the fused decoder.
 // The kernels are templates in dfn_render_kernels.h, instantiated per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip
 // and, for the 128-wide inference program (DFN_WIDTH_128), in dfn_render_{f32,f16,f16x3}_w128.hip; the aux instantiations
-// (RenderArgs.aux: opacity and expected depth next to the RGB) in dfn_render_{f32,f16,f16x3}[_w128]_aux.hip.
+// (RenderArgs.aux: opacity and expected depth next to the RGB) in dfn_render_{f32,f16,f16x3}[_w128]_aux.hip; the instantiations for
+// caller-supplied rays (RenderArgs.use_rays) in dfn_render_{f32,f16,f16x3}[_w128]_rays.hip.
 #include <hip/hip_runtime.h>
 #include "dfn_layout.h"
 #include "dfn_mlp.h"
@@ -29,8 +30,22 @@ hipError_t launch_render_f16x3_aux(const RenderArgs& A, hipStream_t st);
 hipError_t launch_render_f32_w128_aux(const RenderArgs& A, hipStream_t st);
 hipError_t launch_render_f16_w128_aux(const RenderArgs& A, hipStream_t st);
 hipError_t launch_render_f16x3_w128_aux(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f32_rays(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16_rays(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16x3_rays(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f32_w128_rays(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16_w128_rays(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_f16x3_w128_rays(const RenderArgs& A, hipStream_t st);
 
 hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width) {
+    if (A.use_rays) {               // first: a rays launch carries `bounds` in the recorder's samples_out slot (bf16: refused by the API)
+        switch (tier) {
+        case TIER_F32: return width == 128 ? launch_render_f32_w128_rays(A, st) : launch_render_f32_rays(A, st);
+        case TIER_F16: return width == 128 ? launch_render_f16_w128_rays(A, st) : launch_render_f16_rays(A, st);
+        case TIER_F16X3: return width == 128 ? launch_render_f16x3_w128_rays(A, st) : launch_render_f16x3_rays(A, st);
+        default: return hipErrorInvalidValue;
+        }
+    }
     if (A.aux) {                    // (bf16 has no aux kernels; the API refuses it before)
         switch (tier) {
         case TIER_F32: return width == 128 ? launch_render_f32_w128_aux(A, st) : launch_render_f32_aux(A, st);

@@ -1,8 +1,9 @@
 // dfn_render_kernels.h - fused frame renderer and fused decoder for gfx950 (MI355X): the kernel templates.
 // Instantiated once per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip and, for the 128-wide inference program, in
 // dfn_render_{f32,f16,f16x3}_w128.hip; the instantiations that also write opacity and expected depth (TIER_AUX) in
-// dfn_render_{f32,f16,f16x3}[_w128]_aux.hip (separate translation units: they build in parallel); dfn_render.hip dispatches
-// on the tier, the width and the aux switch.
+// dfn_render_{f32,f16,f16x3}[_w128]_aux.hip, the instantiations that render caller-supplied rays (TIER_RAYS) in
+// dfn_render_{f32,f16,f16x3}[_w128]_rays.hip (separate translation units: they build in parallel); dfn_render.hip dispatches
+// on the tier, the width and the aux / rays switches.
 //
 // One wavefront = one ray.  A workgroup of W waves (8 in the bf16 tier, 4 in the f32 tier) walks W rays
 // through: ray generation -> 64 coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
@@ -154,6 +155,13 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // no vector register is live across an MLP pass for them.  The colour arithmetic is untouched: the RGB is the plain kernel's
 // bit for bit.  An aux launch writes no per-sample output (the argument slots of w_head / w_com / z_out carry the aux pointers,
 // dfn_params.h).
+// TIER_RAYS in TW (inference only, never with TIER_AUX): the wave's ray is read from memory instead of being generated
+// (include/dfanerf.h, dfn_render_rays_fwd).  Row r of A.rays is o_head[3], d_head[3] and, in the two-field kernel, o_torso[3],
+// d_torso[3]; directions of any length - norm3 and d / |d| are formed from the loaded values as they are from make_ray's.  The
+// one-field kernel sets the (unused) torso state from the head ray.  A.bounds (optional): (near, far) of ray r for the coarse
+// depths, in place of F.z_near / F.z_far.  The background is indexed by the ray (bg[r]); there is no pixel id.  Only the "this
+// wave's ray" block differs: the ray still lives in the LDS state, so nothing new is live across an MLP pass, and everything
+// after that block - coarse loop, sampler, merge, fine passes, compositing, per-sample outputs, epilogues - is the same code.
 template <int TW, bool TWO, int TRAIN, bool ACT4 = true>
 __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & TIER_MASK)>::THREADS / 256) void render_kernel(
     const RenderArgs A) {
@@ -161,6 +169,9 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     static_assert(HT == 8 || TRAIN == 0, "the 128-wide program is inference only");
     constexpr bool AUX = (TW & TIER_AUX) != 0;
     static_assert(!AUX || TRAIN == 0, "the aux outputs are inference only");
+    constexpr bool RAYS = (TW & TIER_RAYS) != 0;
+    static_assert(!RAYS || TRAIN == 0, "caller-supplied rays are inference only");
+    static_assert(!RAYS || !AUX, "no aux form for caller-supplied rays");
     using C = TierCfg<TIER>;
     using L = KernelLds<TIER, TWO>;
     using P = Prog<TIER, HT>;
@@ -246,7 +257,9 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     const bool valid = r_raw < F.ray_count;
     {
         const int r = valid ? r_raw : F.ray_count - 1;
-        const int pix = A.pix_index ? A.pix_index[r] : F.ray_begin + r;
+        int pix;
+        if constexpr (RAYS) pix = r;                 // the background row of a supplied ray is the ray's own
+        else pix = A.pix_index ? A.pix_index[r] : F.ray_begin + r;
         float bg[3];
         if (A.bg_u8) {
 #pragma unroll
@@ -256,8 +269,24 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             for (int k = 0; k < 3; ++k) bg[k] = A.bg_f32[(size_t)pix * 3 + k];
         }
         float oh[3], dh[3], ot[3], dt[3];
-        make_ray(F.pose, pix, F.W, F.focal, F.cx, F.cy, oh, dh);
-        make_ray(F.pose_body, pix, F.W, F.focal, F.cx, F.cy, ot, dt);
+        float z_near = F.z_near, z_far = F.z_far;
+        if constexpr (RAYS) {
+            const float* row = A.rays + (size_t)r * (TWO ? 12 : 6);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                oh[k] = row[k];
+                dh[k] = row[3 + k];
+                ot[k] = TWO ? row[6 + k] : oh[k];
+                dt[k] = TWO ? row[9 + k] : dh[k];
+            }
+            if (A.bounds) {                          // (uniform over the launch)
+                z_near = A.bounds[(size_t)r * 2];
+                z_far = A.bounds[(size_t)r * 2 + 1];
+            }
+        } else {
+            make_ray(F.pose, pix, F.W, F.focal, F.cx, F.cy, oh, dh);
+            make_ray(F.pose_body, pix, F.W, F.focal, F.cx, F.cy, ot, dt);
+        }
         const float nh = norm3(dh), nt = norm3(dt);
         if (lane == 0) {
 #pragma unroll
@@ -280,7 +309,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
         // coarse z: near*(1-t) + far*t (run_nerf_com_trainExpLater.py:617-618)
         for (int i = lane; i < NC; i += 64) {
             const float t = linspace01(i, NC);
-            zall[i] = add_(mul_(F.z_near, sub_(1.0f, t)), mul_(F.z_far, t));
+            zall[i] = add_(mul_(z_near, sub_(1.0f, t)), mul_(z_far, t));
         }
     }
     __syncthreads();     // bias blob + ray state visible (also drains the first two slab loads)
@@ -828,7 +857,7 @@ template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true, int W128 = 0> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
-    static_assert((W128 & ~(TIER_W128 | TIER_AUX)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux: inference only");      // (W128 also carries TIER_AUX)
+    static_assert((W128 & ~(TIER_W128 | TIER_AUX | TIER_RAYS)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux / rays: inference only");      // (W128 also carries TIER_AUX / TIER_RAYS)
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER, TWO>::TOTAL;
     static bool attr_done = false;
@@ -880,6 +909,12 @@ template <int TIER> static hipError_t launch_render_tier_w128(const RenderArgs& 
 template <int TIER, int W128 = 0> static hipError_t launch_render_tier_aux(const RenderArgs& A, hipStream_t st) {
     if (A.samples_out || !A.aux) return hipErrorInvalidValue;
     return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, W128 | TIER_AUX>(A, st) : launch_render_t<TIER, false, 0, true, W128 | TIER_AUX>(A, st);
+}
+// the instantiations for caller-supplied rays of one tier and width (dfn_render_<tier>[_w128]_rays.hip; inference only: the API
+// offers them in dfn_render_rays_fwd / dfn_render_rays_fwd_u8 alone; the recorder's samples_out slot carries `bounds`)
+template <int TIER, int W128 = 0> static hipError_t launch_render_tier_rays(const RenderArgs& A, hipStream_t st) {
+    if (!A.use_rays || A.aux || !A.rays) return hipErrorInvalidValue;
+    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, W128 | TIER_RAYS>(A, st) : launch_render_t<TIER, false, 0, true, W128 | TIER_RAYS>(A, st);
 }
 template <int TIER> static hipError_t launch_decoder_tier_w128(const DecoderArgs& A, hipStream_t st) {
     if (A.act_T) return hipErrorInvalidValue;

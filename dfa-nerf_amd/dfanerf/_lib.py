@@ -71,6 +71,8 @@ def _load():
         "dfn_render_fwd_u8": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, vp, vp, vp]),
         "dfn_render_fwd_aux": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, fp, vp]),
         "dfn_render_fwd_u8_aux": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
+        "dfn_render_rays_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, fp, fp, fp, fp, fp, vp]),
+        "dfn_render_rays_fwd_u8": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, vp]),
         "dfn_decoder_fwd": (i32, [i32, i32, vp, fp, fp, fp, lg, fp, fp, vp]),
         "dfn_decoder_train_fwd": (i32, [i32, i32, vp, fp, fp, fp, lg, fp, fp, fp, vp, vp, vp]),
         "dfn_get_rays": (i32, [i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), fp, fp, vp]),

@@ -346,13 +346,62 @@ def make_frame(H, W, focal, cx, cy, pose, pose_body, near, far, last_dist=1e10, 
     return fr
 
 
+def pack_rays(o_head, d_head, o_torso=None, d_torso=None):
+    """The `rays` argument of render() / render_u8() (dfn_render_rays_fwd) from ray tensors as get_rays / ndc_rays return them:
+    o_* / d_* [..., 3] each -> contiguous float32 [R, 6] = (o_head, d_head), or [R, 12] = (o_head, d_head, o_torso, d_torso) when the
+    torso pair is given (fields == 2).  The directions need not have unit length."""
+    if (o_torso is None) != (d_torso is None):
+        raise ValueError("pack_rays: o_torso and d_torso come as a pair (both for fields == 2, neither for fields == 1)")
+    parts = [o_head, d_head] + ([o_torso, d_torso] if o_torso is not None else [])
+    rows = []
+    for t in parts:
+        t = torch.as_tensor(t)
+        if t.dim() == 0 or t.shape[-1] != 3:
+            raise ValueError(f"pack_rays: origins and directions are [..., 3] tensors, got {tuple(t.shape)}")
+        rows.append(t.to(dtype=torch.float32, device=rows[0].device if rows else t.device).reshape(-1, 3))
+    if any(r.shape[0] != rows[0].shape[0] for r in rows):
+        raise ValueError(f"pack_rays: mismatched ray counts {[r.shape[0] for r in rows]}")
+    return torch.cat(rows, dim=1).contiguous()
+
+
+def _rays_inputs(who, packed, frame, bg, rays, bounds, **refused):
+    """checks of a rays launch (dfn_render_rays_fwd[_u8]) -> (rays, bounds) as contiguous f32 device tensors"""
+    for name, v in refused.items():
+        if v is not None and v is not False:
+            raise ValueError(f"{who}: rays cannot be combined with {name} ("
+                             + ("supplied rays have no pixel id: gather bg to one row per ray" if name == "pix_index" else
+                                "there is no opacity / depth form of dfn_render_rays_fwd") + ")")
+    n, cols = frame.ray_count, 6 * frame.fields
+    if rays.dim() != 2 or rays.shape[1] != cols:
+        raise ValueError(f"{who}: rays must be [ray_count, {cols}] for fields == {frame.fields} (pack_rays), got {tuple(rays.shape)}")
+    if rays.shape[0] != n:
+        raise ValueError(f"{who}: frame.ray_count = {n} but rays has {rays.shape[0]} rows")
+    if bg.dim() != 2 or bg.shape[0] != n or bg.shape[1] != 3:
+        raise ValueError(f"{who}: with rays, bg is [ray_count, 3] = [{n}, 3] (row r: the background of ray r), got {tuple(bg.shape)}")
+    if not bg.is_contiguous():
+        raise ValueError(f"{who}: bg must be contiguous")
+    if bounds is not None:
+        bounds = _f32c(bounds, packed.device)
+        if tuple(bounds.shape) != (n, 2):
+            raise ValueError(f"{who}: bounds must be [ray_count, 2] = (near, far) per ray, got {tuple(bounds.shape)}")
+    return _f32c(rays, packed.device), bounds
+
+
 def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head=None, out_com=None, want_z=False,
-           want_aux=False):
+           want_aux=False, rays=None, bounds=None):
     """dfn_render_fwd.  bg: f32 [H*W,3] in [0,1] or uint8 [H*W,3] device tensor.
     Returns (rgb_head [n,3], rgb_com [n,3] or None[, w_head, w_com][, z_vals][, aux_head, aux_com]).
     want_aux: dfn_render_fwd_aux - aux_head / aux_com [n,2] = (acc, depth): opacity and premultiplied expected depth of each image
     (include/dfanerf.h); aux_com is None with one field.  Not together with want_weights / want_z: the aux kernels write no
-    per-sample output (reduce the weights of a plain call instead)."""
+    per-sample output (reduce the weights of a plain call instead).
+    rays: dfn_render_rays_fwd - render these rays instead of the frame's pinhole rays: float32 [ray_count, 6 * fields] from
+    pack_rays(); bg is then [ray_count, 3] (row r: the background of ray r) and frame.ray_count must equal the row count (H, W, the
+    intrinsics, the poses and ray_begin of the frame are ignored).  bounds: optional [ray_count, 2] = (near, far) per ray, in place
+    of frame.z_near / z_far.  want_weights / want_z work; pix_index and want_aux do not (ValueError)."""
+    if rays is None and bounds is not None:
+        raise ValueError("render: bounds are per-ray depth ranges of supplied rays (rays=)")
+    if rays is not None:
+        rays, bounds = _rays_inputs("render", packed, frame, bg, rays, bounds, pix_index=pix_index, want_aux=want_aux)
     if want_aux and (want_weights or want_z):
         raise ValueError("render: want_aux cannot be combined with want_weights / want_z (dfn_render_fwd_aux has no per-sample "
                          "outputs; call render() twice, or reduce the weights yourself)")
@@ -384,10 +433,16 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
                                      _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(aux_h),
                                      _ptr(aux_c), _stream()), "dfn_render_fwd_aux")
         return rgb_h, rgb_c, aux_h, aux_c
-    check(lib.dfn_render_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                             _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
-                             _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h),
-                             _ptr(w_c), _ptr(z_v), _stream()), "dfn_render_fwd")
+    if rays is not None:
+        check(lib.dfn_render_rays_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+                                      _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t, _ptr(rays),
+                                      _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h), _ptr(w_c),
+                                      _ptr(z_v), _stream()), "dfn_render_rays_fwd")
+    else:
+        check(lib.dfn_render_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+                                 _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
+                                 _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h),
+                                 _ptr(w_c), _ptr(z_v), _stream()), "dfn_render_fwd")
     out = (rgb_h, rgb_c)
     if want_weights:
         out += (w_h, w_c)
@@ -396,11 +451,18 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     return out
 
 
-def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=None, want_alpha=False, want_depth=False):
+def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=None, want_alpha=False, want_depth=False,
+              rays=None, bounds=None):
     """dfn_render_fwd_u8: the same launch with to8b fused into the epilogue -> uint8 [n,3] images (head, composite).
     want_alpha / want_depth: dfn_render_fwd_u8_aux - the return value grows by (alpha8_head, alpha8_com) uint8 [n] and / or
     (depth16_head, depth16_com) uint16 [n], in this order (the _com entries None with one field); include/dfanerf.h has the
-    formulas.  Without them the plain entry point is the one called."""
+    formulas.  Without them the plain entry point is the one called.
+    rays / bounds: dfn_render_rays_fwd_u8 - as in render(); not together with pix_index / want_alpha / want_depth (ValueError)."""
+    if rays is None and bounds is not None:
+        raise ValueError("render_u8: bounds are per-ray depth ranges of supplied rays (rays=)")
+    if rays is not None:
+        rays, bounds = _rays_inputs("render_u8", packed, frame, bg, rays, bounds, pix_index=pix_index, want_alpha=want_alpha,
+                                    want_depth=want_depth)
     dev = packed.device
     n = frame.ray_count
     two = frame.fields == 2
@@ -432,6 +494,12 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
         if want_depth:
             out += (d_h, d_c)
         return out
+    if rays is not None:
+        check(lib.dfn_render_rays_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
+                                         _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t, _ptr(rays),
+                                         _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(out_h), _ptr(out_c), _stream()),
+              "dfn_render_rays_fwd_u8")
+        return out_h, out_c
     check(lib.dfn_render_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
                                 _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
                                 _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()),

@@ -529,6 +529,39 @@ class FrameRenderer:
                                  want_depth=want_depth)
         return eng.render(pk, bias, fr, self.bg, pix_index=pix_index, out_head=oh, out_com=oc)
 
+    def render_rays(self, rays_head, rays_torso, signal, signal_torso, bg, bounds=None, fields=2, out_u8=False, out=None,
+                    bias=None):
+        """render() for rays the caller supplies (engine.render(rays=): dfn_render_rays_fwd) - what a reference-shaped loop has
+        after get_rays / ndc_rays, sub-pixel offsets, a lens model, or rays of several cameras concatenated.
+        rays_head / rays_torso: (o, d) tensor pairs [..., 3] of the head field's and the torso field's rays (rays_torso is not
+        used with fields == 1 and may be None); directions of any length.  bg: [R, 3] float in [0, 1] or uint8, row r the
+        background of ray r (this renderer's own plate is indexed by pixel and is not used).  bounds: optional [R, 2] =
+        (near, far) per ray; otherwise this renderer's near / far hold for every ray.  The run's tier and width,
+        args.N_samples / n_fine / last_dist / concate_bg, out_u8, out and bias as in render().
+        The f16 guards (check_f16) are NOT re-run here: they calibrate on the pinhole rays of the frames' poses, and rays that
+        leave the volume those rays cover are the caller's to check (f16guard) before rendering them in the f16 / f16x3 tier.
+        -> rgb_head [R,3], rgb_com [R,3] (None if fields == 1)."""
+        eng = self.engine
+        pk = self.decoder.packed(self.tier)
+        if bias is None:
+            bias = pk.fold(signal[0] if isinstance(signal, (list, tuple)) else signal,
+                           signal_torso if fields == 2 else None, self.zs, self.za)
+        if fields == 2 and rays_torso is None:
+            raise ValueError("FrameRenderer.render_rays: fields == 2 needs rays_torso = (o, d)")
+        rays = eng.pack_rays(rays_head[0], rays_head[1], *(rays_torso if fields == 2 else ()))
+        n = rays.shape[0]
+        dev = self.bg.device
+        bg = torch.as_tensor(bg).to(dev).reshape(-1, 3)
+        bg = (bg if bg.dtype == torch.uint8 else bg.float()).contiguous()
+        # (H, W, the intrinsics, the poses and ray_begin are ignored by a rays launch)
+        eye = np.eye(4, dtype=np.float32)
+        fr = eng.make_frame(self.H, self.W, self.focal, self.cx, self.cy, eye, eye, self.near, self.far, self.args.last_dist, 0, n,
+                            self.args.N_samples, self.n_fine, fields, self.args.concate_bg)
+        oh, oc = out if out is not None else (None, None)
+        if out_u8:
+            return eng.render_u8(pk, bias, fr, bg, out_head=oh, out_com=oc, rays=rays.to(dev), bounds=bounds)
+        return eng.render(pk, bias, fr, bg, out_head=oh, out_com=oc, rays=rays.to(dev), bounds=bounds)
+
     def render_image_begin(self, pose, pose_body, signal, signal_torso, fields=2, out_u8=False, bias=None, aux=False):
         """Start a whole frame: render this rank's ray shard and ISSUE the gather (async_op=True: it runs on the backend's
         own stream) -> a handle for render_image_end().  Two sets of shard / gather buffers alternate, so the gather of

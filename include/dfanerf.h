@@ -47,7 +47,7 @@ extern "C" {
  * <= 128: 4 output tiles per trunk layer and half-length K over the hidden vector, 314 instead of 1,138 MFMA fragments per head
  * pass (16-bit tiers; torso 450 instead of 1,306).
  *   - accepted with DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 by dfn_packed_bytes, dfn_pack_weights, dfn_pack_plan, dfn_render_fwd,
- *     dfn_render_fwd_u8 (and their _aux forms) and dfn_decoder_fwd; dfn_bias_floats and dfn_fold_bias accept and ignore it (the bias blob keeps its layout
+ *     dfn_render_fwd_u8 (and their _aux forms), dfn_render_rays_fwd, dfn_render_rays_fwd_u8 and dfn_decoder_fwd; dfn_bias_floats and dfn_fold_bias accept and ignore it (the bias blob keeps its layout
  *     and its 256-float strides: the narrow kernels read the first 128 entries of each hidden-sized vector);
  *   - with DFN_TIER_BF16 (the training tier: it stays padded) and in every other entry point that takes a tier - the training
  *     forwards, the backward streams and kernels, the gradient calls - the result is DFN_E_ARG, before any device work;
@@ -67,7 +67,8 @@ extern "C" {
 
 const char* dfn_last_error(void);
 /* library build info: "dfanerf <version> gfx950".  ABI notes - 0.4: + dfn_render_fwd_aux, dfn_render_fwd_u8_aux (per-ray opacity and
- * expected depth next to the RGB; inference tiers, both widths; nothing else changes).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * expected depth next to the RGB; inference tiers, both widths; nothing else changes); + dfn_render_rays_fwd, dfn_render_rays_fwd_u8
+ * (the fused renderer on caller-supplied rays; inference tiers, both widths; nothing else changes, the version string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -208,6 +209,34 @@ int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_he
                           const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                           const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, uint8_t* alpha8_head,
                           uint8_t* alpha8_com, uint16_t* depth16_head, uint16_t* depth16_com, void* stream);
+
+/* The fused renderer on CALLER-SUPPLIED rays: dfn_render_fwd / dfn_render_fwd_u8 with the ray generation (get_rays, HELP:449-465)
+ * and the launch-wide depth range (MAIN:612-619) replaced by data.  For everything the reference does to its rays between "make
+ * rays" and "render them": ndc_rays, sub-pixel offsets, a lens model, a stereo pair, rays of several cameras in one batch, the
+ * NeRF lineage's per-ray near / far (ray_batch).
+ *   rays    f32 [ray_count, 6 * fields], required.  Row r = o_head[3], d_head[3] and, when fields == 2, o_torso[3], d_torso[3]: the
+ *           ray of the head field (get_rays of poses[img_i], HELP:449-465) and of the torso field (get_rays of pose_body).  The
+ *           directions need not have unit length: as with generated rays, the sample points are o + d * z, the distances between
+ *           samples are multiplied by |d|, and the decoder's view direction is d / |d| (DEC:337).
+ *   bounds  f32 [ray_count, 2] = (near, far) of ray r, optional: the coarse depths of ray r are near * (1 - t) + far * t
+ *           (MAIN:612-619) with that ray's pair.  NULL: frame.z_near / frame.z_far for every ray, as in dfn_render_fwd.
+ *   bg_f32 / bg_u8  [ray_count, 3]: row r is the background of RAY r (there is no pixel id; give one of the two)
+ * Frame fields used: ray_count, n_coarse, n_fine, fields, concate_bg, last_dist, and z_near / z_far when bounds == NULL.  Frame
+ * fields IGNORED: H, W, focal, cx, cy, pose, pose_body, ray_begin (they may hold anything).
+ * Outputs, sample-count / fields / adjacent-bias checks: dfn_render_fwd's (the hierarchical mode needs n_coarse = 64).  Given the
+ * rays dfn_get_rays makes for a pose, bg rows gathered at the same pixels and no bounds (or bounds filled with z_near, z_far), every
+ * output equals dfn_render_fwd's bit for bit: the kernels differ in where the ray comes from, nothing else.
+ * Tiers DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3, with or without DFN_WIDTH_128.  DFN_E_ARG with a message, before any device
+ * work: rays == NULL; DFN_TIER_BF16 (the training tier).  There is NO aux form (opacity / depth) and NO training form of these
+ * entry points. */
+int dfn_render_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                        const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                        const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* weights_head,
+                        float* weights_com, float* z_vals, void* stream);
+/* ... with to8b fused into the epilogue, as dfn_render_fwd_u8: rgb8_* [ray_count,3] uint8. */
+int dfn_render_rays_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                           const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                           const float* bg_f32, const uint8_t* bg_u8, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream);
 
 /* ---- training step: replaces loss.backward() through MAIN:855-899 + DEC:277-349 (torch autograd upstream) ------
  * One step = dfn_train_fwd (the fused renderer with its recorder on: coarse samples, both fields) ->
