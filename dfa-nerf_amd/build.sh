@@ -3,6 +3,8 @@
 #   build.sh          incremental: an object is rebuilt when the HASH of what it is made from changes
 #   build.sh --clean  from scratch
 # An object's stamp = sha256 of its own source, every header of csrc/ and include/, the compiler flags and hipcc's version.
+# The render variants (render_variants.sh) are one source, csrc/dfn_render_variant.hip, compiled once per variant through a
+# stub that build.sh writes into the build directory; a variant's own source is the stub (its defines) plus that file.
 # (Timestamps would reuse a stale object whenever a checkout puts an older header next to a newer .o: the objects travel
 # with the tree to the GPU box, the file times do not mean anything there.)
 set -e
@@ -22,24 +24,27 @@ if [ -n "$DFN_EXTRA_FLAGS" ]; then
   DFN_EXTRA_FLAGS="$DFN_EXTRA_FLAGS -DDFN_DEV_BUILD=1"
 fi
 mkdir -p "$OBJ"
+. "$HERE/render_variants.sh"
 # -pragma-unroll-threshold: the MLP bodies MUST unroll completely (every fragment index, ring slot and recorder dword is a
 # compile-time constant by construction; a loop left rolled puts the fragment ring and the operand vectors into scratch
 # memory) and with the MX-fp8 recorder some bodies exceed LLVM's default budget of 16384 instructions
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-inline-asm -mllvm -pragma-unroll-threshold=200000 -I$SRC -I$HERE/../include $DFN_EXTRA_FLAGS"
 HDR_HASH="$( (cat "$SRC"/*.h "$HERE"/../include/*.h; echo "$FLAGS" | sed "s#$HERE#.#g"; hipcc --version 2>/dev/null | head -2) | sha256sum | cut -d' ' -f1)"
-UNITS="dfn_render dfn_render_f32 dfn_render_bf16 dfn_render_bf16e dfn_render_f16 dfn_render_f16x3 dfn_render_f32_w128 dfn_render_f16_w128 dfn_render_f16x3_w128 dfn_render_f32_aux dfn_render_f16_aux dfn_render_f16x3_aux dfn_render_f32_w128_aux dfn_render_f16_w128_aux dfn_render_f16x3_w128_aux dfn_render_f32_rays dfn_render_f16_rays dfn_render_f16x3_rays dfn_render_f32_w128_rays dfn_render_f16_w128_rays dfn_render_f16x3_w128_rays dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
+UNITS="dfn_render $(variant_units | tr '\n' ' ')dfn_misc dfn_api dfn_train dfn_bwd_bf16 dfn_wgrad_bf16 dfn_signal"
 # the library's own stamp (next to the .so: it travels with it to the GPU box, the object directory does not): everything it
 # is made from, hashed - an up-to-date library is not rebuilt
-LIB_HASH="$( (echo "$HDR_HASH"; cat "$SRC"/*.hip "$SRC"/*.cpp) | sha256sum | cut -d' ' -f1)"
+LIB_HASH="$( (echo "$HDR_HASH"; cat "$SRC"/*.hip "$SRC"/*.cpp "$HERE/render_variants.sh") | sha256sum | cut -d' ' -f1)"
 if [ -f "$OUT" ] && [ "$(cat "$OUT.stamp" 2>/dev/null)" = "$LIB_HASH" ]; then echo "up to date: $OUT"; exit 0; fi
 rm -f "$OUT.stamp"
 pids=()
 for f in $UNITS; do
-  ( want="$HDR_HASH $(sha256sum < "$SRC/$f.hip" | cut -d' ' -f1)"
+  ( src="$SRC/$f.hip"; made="$src"
+    if variant_stub "$f" "$OBJ"; then src="$OBJ/$f.hip"; made="$src $SRC/dfn_render_variant.hip"; fi
+    want="$HDR_HASH $(cat $made | sha256sum | cut -d' ' -f1)"
     if [ ! -f "$OBJ/$f.o" ] || [ "$(cat "$OBJ/$f.stamp" 2>/dev/null)" != "$want" ]; then
       rm -f "$OBJ/$f.stamp"
       EXTRA=""; case "$f" in dfn_render_*|dfn_train|dfn_bwd_bf16) EXTRA="--save-temps=obj";; esac     # keep the ISA of the MLP kernels for the checks below
-      hipcc $FLAGS $EXTRA -c "$SRC/$f.hip" -o "$OBJ/$f.o"
+      hipcc $FLAGS $EXTRA -c "$src" -o "$OBJ/$f.o"
       echo "$want" > "$OBJ/$f.stamp"
     fi ) &
   pids+=($!)
@@ -48,10 +53,10 @@ g++ -O2 -std=c++17 -fPIC -I"$SRC" -I"$HERE/../include" -c "$SRC/dfn_plan.cpp" -o
 for p in "${pids[@]}"; do wait $p; done
 # the asm fragment fetch (DFN_ASM_FETCH) is only safe if nothing touches an in-flight destination register
 # (f16x3: compiler-scheduled fragment reads, checked all the same)
-# (_w128: the 128-wide inference program of the same tier, same rules; _aux: the kernels that also write opacity and depth, same rules;
-# _rays: the kernels for caller-supplied rays, same rules)
-for t in bf16 bf16e f16 f16x3 f16_w128 f16x3_w128 f16_aux f16x3_aux f16_w128_aux f16x3_w128_aux f16_rays f16x3_rays f16_w128_rays f16x3_w128_rays; do
-  ISA="$OBJ/dfn_render_$t-hip-amdgcn-amd-amdhsa-gfx950.s"
+# (every render variant of the 16-bit tiers: the same rules for the 128-wide, the aux and the rays kernels)
+for f in $(variant_units TIER_BF16 TIER_F16 TIER_F16X3); do
+  t="${f#dfn_render_}"
+  ISA="$OBJ/$f-hip-amdgcn-amd-amdhsa-gfx950.s"
   if [ -f "$ISA" ]; then
     python3 "$HERE/../tools/check_inflight.py" "$ISA" || { echo "build.sh: in-flight register hazard in the $t render kernels" >&2; exit 1; }
     # ... and the 16-bit inference kernels must not use scratch memory at all (stack objects, spilled VGPRs).  f16x3 runs one
@@ -66,6 +71,7 @@ for ISA in "$OBJ"/*-hip-amdgcn-amd-amdhsa-gfx950.s; do
 done
 rm -f "$OBJ"/*-hip-amdgcn-*.o "$OBJ"/*.hipi "$OBJ"/*.bc "$OBJ"/*.out "$OBJ"/*.resolution.txt "$OBJ"/*.hipfb "$OBJ"/*-host-*.s      # --save-temps leftovers (the device ISA stays)
 OBJS=""; for f in $UNITS; do OBJS="$OBJS $OBJ/$f.o"; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" $OBJS "$OBJ/dfn_plan.o"
+# --no-undefined: a variant in the dispatch table of dfn_render.hip without an object of that tier and those flags fails HERE
+hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o "$OUT" $OBJS "$OBJ/dfn_plan.o"
 echo "$LIB_HASH" > "$OUT.stamp"
 echo "built $OUT"

@@ -43,6 +43,10 @@ constexpr int TIER_AUX = 0x400;
 // internal, the same way (dfn_render_rays_fwd / dfn_render_rays_fwd_u8 are entry points of their own): the instantiation that reads
 // its rays - origins, directions, optionally per-ray (near, far) - from memory instead of generating pinhole rays.  Never with TIER_AUX
 constexpr int TIER_RAYS = 0x800;
+// a flag of the render variants (dfn_render_variant.hip) only - it never reaches a kernel's first template argument: the 16-bit
+// training forwards whose recorder writes e4m3 (render_kernel<.., ACT4 = false>: RenderArgs.act_e4m3)
+constexpr int TIER_E4M3 = 0x100;
+DFN_HD constexpr bool tier_trainable(int tier) { return tier == TIER_F32 || tier == TIER_BF16; }    // has training kernels (recorder on)
 DFN_HD constexpr bool tier_is16(int tier) { return tier == TIER_BF16 || tier == TIER_F16; }     // 16-bit operand arithmetic
 DFN_HD constexpr bool tier_frag16(int tier) { return tier != TIER_F32; }                       // 16-bit fragment map (E = 8)
 DFN_HD constexpr int tier_split(int tier) { return tier == TIER_F16X3 ? 2 : 1; }                // fragments per k-unit and tile

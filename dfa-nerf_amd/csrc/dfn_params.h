@@ -46,6 +46,8 @@ struct RenderArgs {
 };
 
 static_assert(offsetof(RenderArgs, loss) == offsetof(RenderArgs, act_e4m3) + 8, "use_rays must sit in the padding in front of loss");
+// every render kernel's argument segment is this block: a new variant reuses a slot (the unions above), it moves nothing
+static_assert(sizeof(RenderArgs) == 376 && offsetof(RenderArgs, loss) == 320 && offsetof(RenderArgs, clock_probe) == 368, "RenderArgs layout");
 
 struct DecoderArgs {
     const char* wblob;
@@ -68,5 +70,8 @@ struct DecoderArgs {
 hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width = 256);
 hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st, int width = 256);
 void program_info(int tier, int field, ProgramInfo* out, int width = 256);
+// the launchers of one render variant (dfn_render_kernels.h; instantiated by the variant's object, dfn_render_variant.hip)
+template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st);
+template <int TIER, int FLAGS> hipError_t launch_decoder_tier(const DecoderArgs& A, hipStream_t st);
 
 }  // namespace dfn

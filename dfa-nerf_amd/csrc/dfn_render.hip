@@ -1,8 +1,6 @@
-// dfn_render.hip - tier and width dispatch of the fused frame renderer and the fused decoder.
-// The kernels are templates in dfn_render_kernels.h, instantiated per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip
-// and, for the 128-wide inference program (DFN_WIDTH_128), in dfn_render_{f32,f16,f16x3}_w128.hip; the aux instantiations
-// (RenderArgs.aux: opacity and expected depth next to the RGB) in dfn_render_{f32,f16,f16x3}[_w128]_aux.hip; the instantiations for
-// caller-supplied rays (RenderArgs.use_rays) in dfn_render_{f32,f16,f16x3}[_w128]_rays.hip.
+// dfn_render.hip - tier, width and mode dispatch of the fused frame renderer and the fused decoder.
+// The kernels are templates in dfn_render_kernels.h; each render variant (a tier and a set of flags) is an object of its own,
+// compiled from dfn_render_variant.hip (its header describes the scheme).  This file holds the library's list of them.
 #include <hip/hip_runtime.h>
 #include "dfn_layout.h"
 #include "dfn_mlp.h"
@@ -10,80 +8,46 @@
 
 namespace dfn {
 
-hipError_t launch_render_f32(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_bf16(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3(const RenderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f32(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_decoder_bf16(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f16(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f16x3(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_render_f32_w128(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16_w128(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3_w128(const RenderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f32_w128(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f16_w128(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_decoder_f16x3_w128(const DecoderArgs& A, hipStream_t st);
-hipError_t launch_render_f32_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f32_w128_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16_w128_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3_w128_aux(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f32_rays(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16_rays(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3_rays(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f32_w128_rays(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16_w128_rays(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_f16x3_w128_rays(const RenderArgs& A, hipStream_t st);
+// ---- the variant list: X(tier, flags), one object each (the build's side of it: render_variants.sh) ----
+#define DFN_INFERENCE_VARIANTS(X, T) \
+    X(T, 0) X(T, TIER_W128) X(T, TIER_AUX) X(T, TIER_W128 | TIER_AUX) X(T, TIER_RAYS) X(T, TIER_W128 | TIER_RAYS)
+#define DFN_RENDER_VARIANTS(X) \
+    DFN_INFERENCE_VARIANTS(X, TIER_F32) DFN_INFERENCE_VARIANTS(X, TIER_F16) DFN_INFERENCE_VARIANTS(X, TIER_F16X3) \
+    X(TIER_BF16, 0) X(TIER_BF16, TIER_E4M3)
+
+struct Variant {
+    hipError_t (*render)(const RenderArgs&, hipStream_t);
+    hipError_t (*decoder)(const DecoderArgs&, hipStream_t);
+};
+enum Mode { MODE_PLAIN, MODE_AUX, MODE_RAYS, MODE_E4M3, N_MODES };
+constexpr int N_TIERS = TIER_F16X3 + 1;
+struct VariantTable { Variant at[N_TIERS][2][N_MODES]; };         // [tier][width == 128][mode]; no such variant: null
+static constexpr VariantTable make_table() {
+    VariantTable t{};
+#define X(T, F) \
+    t.at[T][((F) & TIER_W128) != 0][(F) & TIER_RAYS ? MODE_RAYS : (F) & TIER_AUX ? MODE_AUX : (F) & TIER_E4M3 ? MODE_E4M3 : MODE_PLAIN] = \
+        {launch_render_tier<T, (F)>, launch_decoder_tier<T, (F)>};
+    DFN_RENDER_VARIANTS(X)
+#undef X
+    return t;
+}
+static constexpr VariantTable TABLE = make_table();
+static const Variant* variant(int tier, int width, int mode) {
+    if (tier < 0 || tier >= N_TIERS) return nullptr;
+    return &TABLE.at[tier][width == 128][mode];
+}
 
 hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width) {
-    if (A.use_rays) {               // first: a rays launch carries `bounds` in the recorder's samples_out slot (bf16: refused by the API)
-        switch (tier) {
-        case TIER_F32: return width == 128 ? launch_render_f32_w128_rays(A, st) : launch_render_f32_rays(A, st);
-        case TIER_F16: return width == 128 ? launch_render_f16_w128_rays(A, st) : launch_render_f16_rays(A, st);
-        case TIER_F16X3: return width == 128 ? launch_render_f16x3_w128_rays(A, st) : launch_render_f16x3_rays(A, st);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (A.aux) {                    // (bf16 has no aux kernels; the API refuses it before)
-        switch (tier) {
-        case TIER_F32: return width == 128 ? launch_render_f32_w128_aux(A, st) : launch_render_f32_aux(A, st);
-        case TIER_F16: return width == 128 ? launch_render_f16_w128_aux(A, st) : launch_render_f16_aux(A, st);
-        case TIER_F16X3: return width == 128 ? launch_render_f16x3_w128_aux(A, st) : launch_render_f16x3_aux(A, st);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (width == 128) {
-        switch (tier) {
-        case TIER_F32: return launch_render_f32_w128(A, st);
-        case TIER_F16: return launch_render_f16_w128(A, st);
-        case TIER_F16X3: return launch_render_f16x3_w128(A, st);
-        default: return hipErrorInvalidValue;      // (bf16: the training tier stays padded; the API refuses it before)
-        }
-    }
-    switch (tier) {
-    case TIER_BF16: return launch_render_bf16(A, st);
-    case TIER_F16: return launch_render_f16(A, st);
-    case TIER_F16X3: return launch_render_f16x3(A, st);
-    default: return launch_render_f32(A, st);
-    }
+    // rays first: a rays launch carries `bounds` in the recorder's samples_out slot (bf16: refused by the API); then aux (bf16 has no
+    // aux kernels; the API refuses it before); then the width (bf16: the training tier stays padded; the API refuses it before).
+    // The 16-bit training step with the e4m3 opt-out for act_T: those two kernels are a variant of their own
+    const int mode = A.use_rays ? MODE_RAYS : A.aux ? MODE_AUX : (tier == TIER_BF16 && A.samples_out && A.act_e4m3) ? MODE_E4M3 : MODE_PLAIN;
+    const Variant* v = variant(tier, width, mode);
+    return v && v->render ? v->render(A, st) : hipErrorInvalidValue;
 }
 hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st, int width) {
-    if (width == 128) {
-        switch (tier) {
-        case TIER_F32: return launch_decoder_f32_w128(A, st);
-        case TIER_F16: return launch_decoder_f16_w128(A, st);
-        case TIER_F16X3: return launch_decoder_f16x3_w128(A, st);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (tier) {
-    case TIER_BF16: return launch_decoder_bf16(A, st);
-    case TIER_F16: return launch_decoder_f16(A, st);
-    case TIER_F16X3: return launch_decoder_f16x3(A, st);
-    default: return launch_decoder_f32(A, st);
-    }
+    const Variant* v = variant(tier, width, MODE_PLAIN);
+    return v && v->decoder ? v->decoder(A, st) : hipErrorInvalidValue;
 }
 
 // the 16-bit tiers share one program (same fragment counts and bias blob)
@@ -99,22 +63,12 @@ void program_info(int tier, int field, ProgramInfo* out, int width) {
                : tier == TIER_F32 ? info_of<Prog<TIER_F32, 4>>(field) : info_of<Prog<TIER_F16, 4>>(field);
         return;
     }
-    if (tier == TIER_F16X3) {       // the f16 program with two fragments (hi, lo') per k-unit and tile; the same bias blob
-        using P = Prog<TIER_F16X3>;
-        static_assert(P::H_FRAGS == 2 * Prog<TIER_F16>::H_FRAGS && P::T_FRAGS == 2 * Prog<TIER_F16>::T_FRAGS, "f16x3 stream");
-        static_assert(P::H_NBIAS == Prog<TIER_F16>::H_NBIAS && P::T_NBIAS == Prog<TIER_F16>::T_NBIAS, "f16x3 bias blob");
-        *out = field == FIELD_TORSO ? ProgramInfo{P::T_FRAGS, P::T_SLABS, P::T_NBIAS}
-                                    : ProgramInfo{P::H_FRAGS, P::H_SLABS, P::H_NBIAS};
-    } else if (tier != TIER_F32) {
-        using P = Prog<TIER_BF16>;
-        static_assert(Prog<TIER_F16>::H_FRAGS == P::H_FRAGS && Prog<TIER_F16>::T_FRAGS == P::T_FRAGS, "16-bit tiers");
-        *out = field == FIELD_TORSO ? ProgramInfo{P::T_FRAGS, P::T_SLABS, P::T_NBIAS}
-                                    : ProgramInfo{P::H_FRAGS, P::H_SLABS, P::H_NBIAS};
-    } else {
-        using P = Prog<TIER_F32>;
-        *out = field == FIELD_TORSO ? ProgramInfo{P::T_FRAGS, P::T_SLABS, P::T_NBIAS}
-                                    : ProgramInfo{P::H_FRAGS, P::H_SLABS, P::H_NBIAS};
-    }
+    // f16x3: the f16 program with two fragments (hi, lo') per k-unit and tile; the same bias blob
+    static_assert(Prog<TIER_F16X3>::H_FRAGS == 2 * Prog<TIER_F16>::H_FRAGS && Prog<TIER_F16X3>::T_FRAGS == 2 * Prog<TIER_F16>::T_FRAGS, "f16x3 stream");
+    static_assert(Prog<TIER_F16X3>::H_NBIAS == Prog<TIER_F16>::H_NBIAS && Prog<TIER_F16X3>::T_NBIAS == Prog<TIER_F16>::T_NBIAS, "f16x3 bias blob");
+    static_assert(Prog<TIER_F16>::H_FRAGS == Prog<TIER_BF16>::H_FRAGS && Prog<TIER_F16>::T_FRAGS == Prog<TIER_BF16>::T_FRAGS, "16-bit tiers");
+    *out = tier == TIER_F16X3 ? info_of<Prog<TIER_F16X3>>(field)
+           : tier == TIER_F32 ? info_of<Prog<TIER_F32>>(field) : info_of<Prog<TIER_BF16>>(field);
 }
 
 }  // namespace dfn

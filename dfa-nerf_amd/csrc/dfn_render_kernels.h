@@ -1,9 +1,7 @@
 // dfn_render_kernels.h - fused frame renderer and fused decoder for gfx950 (MI355X): the kernel templates.
-// Instantiated once per precision tier in dfn_render_{f32,bf16,f16,f16x3}.hip and, for the 128-wide inference program, in
-// dfn_render_{f32,f16,f16x3}_w128.hip; the instantiations that also write opacity and expected depth (TIER_AUX) in
-// dfn_render_{f32,f16,f16x3}[_w128]_aux.hip, the instantiations that render caller-supplied rays (TIER_RAYS) in
-// dfn_render_{f32,f16,f16x3}[_w128]_rays.hip (separate translation units: they build in parallel); dfn_render.hip dispatches
-// on the tier, the width and the aux / rays switches.
+// Instantiated per render variant - a precision tier and a set of flags (width, aux, rays) - each an object of its own, all from one
+// source: dfn_render_variant.hip, whose header describes the scheme; dfn_render.hip dispatches on the tier, the width and the
+// aux / rays switches.
 //
 // One wavefront = one ray.  A workgroup of W waves (8 in the bf16 tier, 4 in the f32 tier) walks W rays
 // through: ray generation -> 64 coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
@@ -142,7 +140,7 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // the recorder on, the coarse points in the coarse pass, the fine points in the fine passes, recorded in evaluation
 // order; the backward gets the merged depths and each point's merged rank to composite them in depth order)
 // ACT4 (training forwards only): the recorder writes act_T as MX-fp4 (the default of the fused step) or as MX-fp8 e4m3 (the
-// run-time opt-out: DFN_TRAIN_ACT_E4M3 or'ed into the tier of the dfn_train_fwd* calls; instantiated in dfn_render_bf16e.hip)
+// run-time opt-out: DFN_TRAIN_ACT_E4M3 or'ed into the tier of the dfn_train_fwd* calls; the TIER_E4M3 variant)
 // TW: the tier, with the width flag of the C ABI or'ed in (TIER_W128 == DFN_WIDTH_128: the 128-wide inference program, HT = 4 hidden
 // tiles - dfn_mlp.h Prog<TIER, HT>).  Only the MLP passes differ between the widths: sampler, compositing, epilogues, LDS layout, ring,
 // workgroup shape and block mapping are the same code.  (The flag rides in the tier argument here as it does in the ABI: the 256-wide
@@ -852,7 +850,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- per-tier launchers (instantiated by dfn_render_<tier>.hip; W128 = TIER_W128: the 128-wide program, dfn_render_<tier>_w128.hip)
+// ---- launchers (W128 = the flags or'ed into the kernel's TW: TIER_W128, TIER_AUX, TIER_RAYS)
 template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
@@ -886,47 +884,39 @@ template <int TIER, bool TORSO, bool REC = false, int W128 = 0> static hipError_
     return hipGetLastError();
 }
 
-hipError_t launch_train_bf16_e4m3(const RenderArgs& A, hipStream_t st);      // dfn_render_bf16e.hip
-// all launches of one tier; TRAINABLE: the tier has a training forward (recorder on)
-template <int TIER, bool TRAINABLE> static hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st) {
-    const bool two = A.frame.fields == 2;
-    if (A.samples_out) {     // training step: two fields, recorder on; coarse only (MAIN:855-899) or hierarchical (row H)
-        if constexpr (TRAINABLE) {
-            // 16-bit tier with the e4m3 opt-out for act_T: those two kernels are a translation unit of their own
-            if (TIER == TIER_BF16 && A.act_e4m3) return launch_train_bf16_e4m3(A, st);
-            return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2>(A, st) : launch_render_t<TIER, true, 1>(A, st);
-        } else return hipErrorInvalidValue;
+// every launch of one render variant (tier, flags: dfn_render_variant.hip).  FLAGS == 0: the 256-wide program of the tier - inference
+// and, in a trainable tier, the training forwards (recorder on).  Every other variant is inference only and holds the kernels of its
+// flags alone: TIER_W128 (the API refuses DFN_WIDTH_128 in every training entry point), TIER_AUX (dfn_render_fwd_aux /
+// dfn_render_fwd_u8_aux), TIER_RAYS (dfn_render_rays_fwd / dfn_render_rays_fwd_u8; the recorder's samples_out slot carries `bounds`),
+// the last two with or without TIER_W128.  TIER_E4M3: the two 16-bit training forwards whose recorder writes act_T as MX-fp8 e4m3
+// (the run-time opt-out of the narrow activation format, for A/B runs of the two formats on real data in one process), nothing else.
+template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st) {
+    if constexpr (FLAGS == TIER_E4M3) {
+        return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2, false>(A, st) : launch_render_t<TIER, true, 1, false>(A, st);
+    } else {
+        if constexpr ((FLAGS & TIER_RAYS) != 0) {
+            if (!A.use_rays || A.aux || !A.rays) return hipErrorInvalidValue;
+        } else if constexpr ((FLAGS & TIER_AUX) != 0) {
+            if (A.samples_out || !A.aux) return hipErrorInvalidValue;
+        } else if (A.samples_out) {     // training step: two fields, recorder on; coarse only (MAIN:855-899) or hierarchical (row H)
+            if constexpr (FLAGS == 0 && tier_trainable(TIER))
+                return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2>(A, st) : launch_render_t<TIER, true, 1>(A, st);
+            else return hipErrorInvalidValue;
+        }
+        return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, FLAGS>(A, st) : launch_render_t<TIER, false, 0, true, FLAGS>(A, st);
     }
-    return two ? launch_render_t<TIER, true>(A, st) : launch_render_t<TIER, false>(A, st);
 }
-// the 128-wide program of one tier (inference only: the API refuses DFN_WIDTH_128 in every training entry point)
-template <int TIER> static hipError_t launch_render_tier_w128(const RenderArgs& A, hipStream_t st) {
-    if (A.samples_out) return hipErrorInvalidValue;
-    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, TIER_W128>(A, st) : launch_render_t<TIER, false, 0, true, TIER_W128>(A, st);
-}
-// the aux instantiations of one tier and width (dfn_render_<tier>[_w128]_aux.hip; inference only: the API offers them in
-// dfn_render_fwd_aux / dfn_render_fwd_u8_aux alone)
-template <int TIER, int W128 = 0> static hipError_t launch_render_tier_aux(const RenderArgs& A, hipStream_t st) {
-    if (A.samples_out || !A.aux) return hipErrorInvalidValue;
-    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, W128 | TIER_AUX>(A, st) : launch_render_t<TIER, false, 0, true, W128 | TIER_AUX>(A, st);
-}
-// the instantiations for caller-supplied rays of one tier and width (dfn_render_<tier>[_w128]_rays.hip; inference only: the API
-// offers them in dfn_render_rays_fwd / dfn_render_rays_fwd_u8 alone; the recorder's samples_out slot carries `bounds`)
-template <int TIER, int W128 = 0> static hipError_t launch_render_tier_rays(const RenderArgs& A, hipStream_t st) {
-    if (!A.use_rays || A.aux || !A.rays) return hipErrorInvalidValue;
-    return A.frame.fields == 2 ? launch_render_t<TIER, true, 0, true, W128 | TIER_RAYS>(A, st) : launch_render_t<TIER, false, 0, true, W128 | TIER_RAYS>(A, st);
-}
-template <int TIER> static hipError_t launch_decoder_tier_w128(const DecoderArgs& A, hipStream_t st) {
-    if (A.act_T) return hipErrorInvalidValue;
-    return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true, false, TIER_W128>(A, st) : launch_decoder_t<TIER, false, false, TIER_W128>(A, st);
-}
-template <int TIER, bool TRAINABLE> static hipError_t launch_decoder_tier(const DecoderArgs& A, hipStream_t st) {
-    if (A.act_T) {           // training forward on explicit points: recorder on
-        if constexpr (TRAINABLE)
-            return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true, true>(A, st) : launch_decoder_t<TIER, false, true>(A, st);
-        else return hipErrorInvalidValue;
+// the decoder on explicit points has a plain and a 128-wide form only: every other variant holds no decoder kernel and refuses
+template <int TIER, int FLAGS> hipError_t launch_decoder_tier(const DecoderArgs& A, hipStream_t st) {
+    if constexpr ((FLAGS & ~TIER_W128) != 0) return hipErrorInvalidValue;
+    else {
+        if (A.act_T) {           // training forward on explicit points: recorder on
+            if constexpr (FLAGS == 0 && tier_trainable(TIER))
+                return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true, true>(A, st) : launch_decoder_t<TIER, false, true>(A, st);
+            else return hipErrorInvalidValue;
+        }
+        return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true, false, FLAGS>(A, st) : launch_decoder_t<TIER, false, false, FLAGS>(A, st);
     }
-    return A.field == FIELD_TORSO ? launch_decoder_t<TIER, true>(A, st) : launch_decoder_t<TIER, false>(A, st);
 }
 
 }  // namespace dfn

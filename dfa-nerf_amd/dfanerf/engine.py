@@ -387,6 +387,27 @@ def _rays_inputs(who, packed, frame, bg, rays, bounds, **refused):
     return _f32c(rays, packed.device), bounds
 
 
+def _launch_inputs(who, dtype, packed, bias, frame, bg, pix_index, out_head, out_com):
+    """What every dfn_render* entry point takes, for render() (dtype float32) and render_u8() (uint8) ->
+    (net, bgs, pix_index, out_head, out_com): net = the leading arguments (tier, frame, packed head, packed torso, bias, bias_t),
+    bgs = the (bg_f32, bg_u8) pair, pix_index as an int32 device tensor (or None), the two images (given or allocated)."""
+    dev, n, two = packed.device, frame.ray_count, frame.fields == 2
+    out_h = out_head if out_head is not None else torch.empty(n, 3, dtype=dtype, device=dev)
+    out_c = (out_com if out_com is not None else torch.empty(n, 3, dtype=dtype, device=dev)) if two else None
+    for o in (out_h, out_c):
+        if o is not None and (o.dtype != dtype or not o.is_contiguous() or o.numel() != n * 3):
+            raise ValueError(f"{who}: output buffers must be contiguous {str(dtype).split('.')[-1]} [ray_count, 3]")
+    if bg.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("bg must be float32 or uint8")
+    bgs = (_ptr(bg) if bg.dtype == torch.float32 else None, _ptr(bg) if bg.dtype == torch.uint8 else None)
+    bias_t = C.c_void_p(bias.data_ptr() + 4 * packed.bias_floats(FIELD_HEAD)) if two else None
+    if pix_index is not None:
+        pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
+    net = (packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]), _ptr(packed.packed.get(FIELD_TORSO)) if two else None,
+           _ptr(bias), bias_t)
+    return net, bgs, pix_index, out_h, out_c
+
+
 def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head=None, out_com=None, want_z=False,
            want_aux=False, rays=None, bounds=None):
     """dfn_render_fwd.  bg: f32 [H*W,3] in [0,1] or uint8 [H*W,3] device tensor.
@@ -405,44 +426,23 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     if want_aux and (want_weights or want_z):
         raise ValueError("render: want_aux cannot be combined with want_weights / want_z (dfn_render_fwd_aux has no per-sample "
                          "outputs; call render() twice, or reduce the weights yourself)")
-    dev = packed.device
-    n = frame.ray_count
-    two = frame.fields == 2
-    rgb_h = out_head if out_head is not None else torch.empty(n, 3, dtype=torch.float32, device=dev)
-    rgb_c = (out_com if out_com is not None else torch.empty(n, 3, dtype=torch.float32, device=dev)) if two else None
-    for o in (rgb_h, rgb_c):
-        if o is not None and (o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != n * 3):
-            raise ValueError("render: output buffers must be contiguous float32 [ray_count, 3]")
+    net, bgs, pix_index, rgb_h, rgb_c = _launch_inputs("render", torch.float32, packed, bias, frame, bg, pix_index, out_head, out_com)
+    dev, n, two = packed.device, frame.ray_count, frame.fields == 2
+    if want_aux:
+        aux_h = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        aux_c = torch.empty(n, 2, dtype=torch.float32, device=dev) if two else None
+        check(lib.dfn_render_fwd_aux(*net, *bgs, _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(aux_h), _ptr(aux_c), _stream()),
+              "dfn_render_fwd_aux")
+        return rgb_h, rgb_c, aux_h, aux_c
     S = frame.n_coarse + frame.n_fine
     w_h = torch.empty(n, S, dtype=torch.float32, device=dev) if want_weights else None
     w_c = torch.empty(n, S, dtype=torch.float32, device=dev) if (want_weights and two) else None
     z_v = torch.empty(n, S, dtype=torch.float32, device=dev) if want_z else None
-    bg_f32 = bg if bg.dtype == torch.float32 else None
-    bg_u8 = bg if bg.dtype == torch.uint8 else None
-    if bg_f32 is None and bg_u8 is None:
-        raise TypeError("bg must be float32 or uint8")
-    nh = packed.bias_floats(FIELD_HEAD)
-    bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
-    if pix_index is not None:
-        pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
-    if want_aux:
-        aux_h = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        aux_c = torch.empty(n, 2, dtype=torch.float32, device=dev) if two else None
-        check(lib.dfn_render_fwd_aux(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                     _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
-                                     _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(aux_h),
-                                     _ptr(aux_c), _stream()), "dfn_render_fwd_aux")
-        return rgb_h, rgb_c, aux_h, aux_c
+    outs = (_ptr(rgb_h), _ptr(rgb_c), _ptr(w_h), _ptr(w_c), _ptr(z_v), _stream())
     if rays is not None:
-        check(lib.dfn_render_rays_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                      _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t, _ptr(rays),
-                                      _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h), _ptr(w_c),
-                                      _ptr(z_v), _stream()), "dfn_render_rays_fwd")
+        check(lib.dfn_render_rays_fwd(*net, _ptr(rays), _ptr(bounds), *bgs, *outs), "dfn_render_rays_fwd")
     else:
-        check(lib.dfn_render_fwd(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                 _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
-                                 _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c), _ptr(w_h),
-                                 _ptr(w_c), _ptr(z_v), _stream()), "dfn_render_fwd")
+        check(lib.dfn_render_fwd(*net, *bgs, _ptr(pix_index), *outs), "dfn_render_fwd")
     out = (rgb_h, rgb_c)
     if want_weights:
         out += (w_h, w_c)
@@ -463,31 +463,15 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
     if rays is not None:
         rays, bounds = _rays_inputs("render_u8", packed, frame, bg, rays, bounds, pix_index=pix_index, want_alpha=want_alpha,
                                     want_depth=want_depth)
-    dev = packed.device
-    n = frame.ray_count
-    two = frame.fields == 2
-    out_h = out_head if out_head is not None else torch.empty(n, 3, dtype=torch.uint8, device=dev)
-    out_c = (out_com if out_com is not None else torch.empty(n, 3, dtype=torch.uint8, device=dev)) if two else None
-    for o in (out_h, out_c):
-        if o is not None and (o.dtype != torch.uint8 or not o.is_contiguous() or o.numel() != n * 3):
-            raise ValueError("render_u8: output buffers must be contiguous uint8 [ray_count, 3]")
-    bg_f32 = bg if bg.dtype == torch.float32 else None
-    bg_u8 = bg if bg.dtype == torch.uint8 else None
-    if bg_f32 is None and bg_u8 is None:
-        raise TypeError("bg must be float32 or uint8")
-    nh = packed.bias_floats(FIELD_HEAD)
-    bias_t = C.c_void_p(bias.data_ptr() + 4 * nh) if two else None
-    if pix_index is not None:
-        pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
+    net, bgs, pix_index, out_h, out_c = _launch_inputs("render_u8", torch.uint8, packed, bias, frame, bg, pix_index, out_head, out_com)
+    dev, n, two = packed.device, frame.ray_count, frame.fields == 2
     if want_alpha or want_depth:
         a_h = torch.empty(n, dtype=torch.uint8, device=dev) if want_alpha else None
         a_c = torch.empty(n, dtype=torch.uint8, device=dev) if (want_alpha and two) else None
         d_h = torch.empty(n, dtype=torch.uint16, device=dev) if want_depth else None
         d_c = torch.empty(n, dtype=torch.uint16, device=dev) if (want_depth and two) else None
-        check(lib.dfn_render_fwd_u8_aux(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                        _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
-                                        _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _ptr(a_h), _ptr(a_c),
-                                        _ptr(d_h), _ptr(d_c), _stream()), "dfn_render_fwd_u8_aux")
+        check(lib.dfn_render_fwd_u8_aux(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), _ptr(a_h), _ptr(a_c), _ptr(d_h),
+                                        _ptr(d_c), _stream()), "dfn_render_fwd_u8_aux")
         out = (out_h, out_c)
         if want_alpha:
             out += (a_h, a_c)
@@ -495,15 +479,9 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
             out += (d_h, d_c)
         return out
     if rays is not None:
-        check(lib.dfn_render_rays_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                         _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t, _ptr(rays),
-                                         _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(out_h), _ptr(out_c), _stream()),
-              "dfn_render_rays_fwd_u8")
-        return out_h, out_c
-    check(lib.dfn_render_fwd_u8(packed.tier_arg, C.byref(frame), _ptr(packed.packed[FIELD_HEAD]),
-                                _ptr(packed.packed.get(FIELD_TORSO)) if two else None, _ptr(bias), bias_t,
-                                _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()),
-          "dfn_render_fwd_u8")
+        check(lib.dfn_render_rays_fwd_u8(*net, _ptr(rays), _ptr(bounds), *bgs, _ptr(out_h), _ptr(out_c), _stream()), "dfn_render_rays_fwd_u8")
+    else:
+        check(lib.dfn_render_fwd_u8(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()), "dfn_render_fwd_u8")
     return out_h, out_c
 
 

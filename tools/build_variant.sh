@@ -3,7 +3,8 @@
 # (the in-tree library is untouched); select it at run time with DFN_LIB=exp_libs/<name>.so.
 #   tools/build_variant.sh timing -DDFN_TIMING
 # Only the 16-bit render translation units are recompiled with the flags (the experiments live there); everything else
-# is linked from the in-tree objects (run dfa-nerf_amd/build.sh first).  VARIANT_UNITS overrides the list.
+# is linked from the in-tree objects (run dfa-nerf_amd/build.sh first).  VARIANT_UNITS overrides the list: render variants
+# (dfa-nerf_amd/render_variants.sh: dfn_render_<name>) or plain units of csrc/.
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 NAME="$1"; shift
@@ -11,11 +12,13 @@ SRC="$ROOT/dfa-nerf_amd/csrc"
 BASE="$ROOT/dfa-nerf_amd/build"
 OBJ="$ROOT/exp_libs/obj_$NAME"
 mkdir -p "$OBJ"
+. "$ROOT/dfa-nerf_amd/render_variants.sh"
 UNITS="${VARIANT_UNITS:-dfn_render_f16 dfn_render_bf16}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-inline-asm -mllvm -pragma-unroll-threshold=200000 -I$SRC -I$ROOT/include -DDFN_DEV_BUILD=1 $*"
 pids=()
 for f in $UNITS; do
-  ( hipcc $FLAGS --save-temps=obj -c "$SRC/$f.hip" -o "$OBJ/$f.o" 2>"$OBJ/$f.log" ) &
+  src="$SRC/$f.hip"; if variant_stub "$f" "$OBJ"; then src="$OBJ/$f.hip"; fi
+  ( hipcc $FLAGS --save-temps=obj -c "$src" -o "$OBJ/$f.o" 2>"$OBJ/$f.log" ) &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p || { cat "$OBJ"/*.log; exit 1; }; done
