@@ -5,6 +5,7 @@
 // consumes G*KU fragments in [ku][g] order; here emit_group() appends the same fragments.  The plan is pure
 // host code (no GPU needed), so tests/test_pack_plan.py can emulate the kernel's dataflow on the CPU
 // from the plan alone and compare with the oracle.
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <vector>
@@ -175,7 +176,7 @@ struct GM {   // GradMap
 };
 }  // namespace
 
-void build_wgrad_plan(int field, std::vector<WOpHost>& ops, std::vector<int32_t>& map, std::vector<int32_t>& bias_rows) {
+void build_wgrad_plan(int field, std::vector<WOp>& ops, std::vector<int32_t>& map, std::vector<int32_t>& bias_rows) {
     ops.clear();
     map.clear();
     bias_rows.clear();
@@ -191,9 +192,9 @@ void build_wgrad_plan(int field, std::vector<WOpHost>& ops, std::vector<int32_t>
     };
     auto add = [&](int a_row, int M, int b_row, int N, const RowFn& rows, const ColFn& cols) {
         int owner = 1;      // dy_T row ranges are either identical or disjoint between GEMMs
-        for (const WOpHost& q : ops)
+        for (const WOp& q : ops)
             if (q.a_row == a_row) owner = 0;
-        WOpHost o{a_row, M, b_row, N, (int)map.size(), owner};
+        WOp o{a_row, M, b_row, N, (int)map.size(), owner};
         ops.push_back(o);
         for (int m = 0; m < M; ++m) {
             const Src src = rows(m);
@@ -250,9 +251,9 @@ void build_wgrad_plan(int field, std::vector<WOpHost>& ops, std::vector<int32_t>
         // the fused weight+bias gradient pass produces a row block's sums in the GEMM that reads it; a block that no
         // GEMM reads (its layer multiplies a per-frame constant only, e.g. fc_signal_skips) gets a GEMM with N = 0
         bool read = false;
-        for (const WOpHost& q : ops)
+        for (const WOp& q : ops)
             if (q.a_row <= row0 && row0 + n <= q.a_row + q.M) read = true;
-        if (!read) ops.push_back(WOpHost{row0, n, 0, 0, (int)map.size(), 1});
+        if (!read) ops.push_back(WOp{row0, n, 0, 0, (int)map.size(), 1});
     };
     if (torso) {
         const int seq[14] = {GM::S_DE0, GM::S_DS0, GM::S_DE1, GM::S_DS1, GM::S_DE2, GM::S_DS2, GM::S_DE3, GM::S_GE3,
@@ -266,6 +267,119 @@ void build_wgrad_plan(int field, std::vector<WOpHost>& ops, std::vector<int32_t>
     vec(gt + GM::T_DYV, 256);                                   // VIEW: feat_view rows ...
     vec(gt + GM::T_DSIG, 32);                                   // ... + the sigma tile
     vec(gt + GM::T_DYO, 32);                                    // OUT
+}
+
+// ---- the launches planned from that list (what dfn_api.hip uploads) ------------------------------------------------------
+// f32 tier: every GEMM is cut into `ksplit` slices of the points (one partial array per slice: the reduction adds
+// the same number of slices for every element).  Items of the narrow launch: blocks of a shape's row tiles x slices,
+// the shapes with the longest workgroups first (dfn_plan.h: WN_4x4 < WN_4x2 < ... is that order)
+std::string wgrad_f32_plan(const std::vector<WOp>& ops, int ksplit, std::vector<int>& full_ops, std::vector<WNItem>& nitems) {
+    std::string error;
+    full_ops.clear();
+    nitems.clear();
+    for (int shape = 0; shape < WN_COUNT; ++shape)
+        for (size_t i = 0; i < ops.size(); ++i) {
+            const WOp& o = ops[i];
+            const int sh = wn_shape_of(o.M, o.N);
+            if (sh == -2) error = "weight-gradient GEMM " + std::to_string(o.M) + " x " + std::to_string(o.N) + ": no f32 kernel for this shape";
+            if (sh == -1 && shape == 0) full_ops.push_back((int)i);
+            if (sh != shape) continue;
+            for (int m0 = 0; m0 < o.M / 32; m0 += wn_shape_mt(shape))
+                for (int ks = 0; ks < ksplit; ++ks) nitems.push_back(WNItem{(int)i, ks, m0, shape});
+        }
+    return error;
+}
+
+// 16-bit tier.  head 16 / torso 18 (round 3, whole step, interleaved A/B over 600 steps x 4: torso 16 / 17 / 18 / 20 = 1.1056 / 1.1021 / 1.0975 /
+// 1.114 ms; head 19: worse).  Round 2: the kernel alone takes the same time for 16 ... 32 slices (0.81-0.82 ms for both fields, HBM-bound), the second stage
+// reads a third less and the whole training step is 1.2 % faster than with 24 (interleaved A/B, bench.py --workload c4)
+// Balanced split (round 4).  Round 3 cut every GEMM into the same 16 / 18 slices of the points: the head's 13 GEMMs made 208
+// workgroups on 256 compute units - ONE round, whose length is the 256 x 256 GEMMs' (512 operand bytes per point, 128 steps)
+// while the workgroups of the narrow GEMMs (288-320 bytes per point) finished early and 48 compute units had none.  Now the
+// number of slices of a GEMM is proportional to its operand rows M + N, so that every workgroup streams about the same bytes
+// and the launch fills the chip's compute units once: head 23 slices for a 256 x 256 GEMM (89 steps), 13-14 for the narrow
+// ones.  `uniform` (DFN_WGRAD_KSPLIT[_H|_T], developer overrides) selects a uniform split instead.
+void wgrad_split(const std::vector<WOp>& ops, int uniform, int target_wgs, std::vector<WItem>& items, std::vector<int>& n_of) {
+    // cost of a GEMM per point: its operand bytes; a floor for the narrow ones (a step of theirs costs a barrier and a DMA
+    // round trip whatever it moves)
+    // (a GEMM with N = 0 only sums the rows of its dY block; it runs the general loop: measured 51 us where a 256 x 256 GEMM
+    // takes 142 - tools/wl_trace.py)
+    // Measured per-workgroup time x slices (tools/wl_trace.py with the MX-fp4 activations, us x slices / 5): a dY row costs 1, an
+    // activation row 1/2 (32 vs 16 bytes per point tile) - 256 x 256: 380, 256 x 128: 326, 256 x 64: 286, 64 x 64: 94 - except
+    // the shapes whose steps are latency- rather than byte-bound: 256 x 32: 244, 32 x 256: 164, N = 0 (M = 64): 180
+    auto cost = [](const WOp& o) {
+        if (o.N == 0) return 2.8 * o.M;
+        if (o.M == 256 && o.N == 32) return 245.0;
+        if (o.M == 32 && o.N == 256) return 170.0;
+        return (double)std::max(o.M + o.N / 2, 90);
+    };
+    double total = 0;
+    for (const WOp& o : ops) total += cost(o);
+    n_of.assign(ops.size(), 1);
+    int sum = 0;
+    for (size_t i = 0; i < ops.size(); ++i) {
+        n_of[i] = uniform ? uniform : std::min(32, std::max(1, (int)(target_wgs * cost(ops[i]) / total)));     // (floor: the sum stays <= target)
+        sum += n_of[i];
+    }
+    // hand the workgroups the floor left over to the GEMMs with the most bytes per workgroup
+    while (!uniform && sum < target_wgs) {
+        int best = -1;
+        double worst = 0;
+        for (size_t i = 0; i < ops.size(); ++i)
+            if (n_of[i] < 32 && cost(ops[i]) / n_of[i] > worst) worst = cost(ops[i]) / n_of[i], best = (int)i;
+        if (best < 0) break;
+        ++n_of[best];
+        ++sum;
+    }
+    std::vector<int> order(ops.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost(ops[a]) / n_of[a] > cost(ops[b]) / n_of[b]; });
+    items.clear();
+    for (int op : order)
+        for (int k = 0; k < n_of[op]; ++k) items.push_back(WItem{op, k, n_of[op], 0});
+}
+
+// slices per 256-element block of C (every GEMM's C region is a multiple of 1024 elements: one GEMM per block) and
+// per bias element (the GEMM that owns its dy_T row block)
+const char* wgrad_slice_tables(const std::vector<WOp>& ops, const std::vector<int>& n_of, size_t c_elems,
+                               const std::vector<int32_t>& bias_rows, std::vector<unsigned char>& blk_n,
+                               std::vector<unsigned char>& bias_n) {
+    blk_n.assign((c_elems + 255) / 256, 1);
+    bias_n.assign(bias_rows.size(), 1);
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const WOp& o = ops[i];
+        if (o.c_off % 256) return "internal: a GEMM's C region is not block-aligned";
+        for (long bb = o.c_off / 256; bb < (o.c_off + (long)o.M * o.N + 255) / 256; ++bb) blk_n[bb] = (unsigned char)n_of[i];
+        if (o.bias_owner)
+            for (size_t e = 0; e < bias_rows.size(); ++e)
+                if (bias_rows[e] >= o.a_row && bias_rows[e] < o.a_row + o.M) bias_n[e] = (unsigned char)n_of[i];
+    }
+    return nullptr;
+}
+
+// inverse of the bias row table: dy_T row -> bias element (each row feeds at most one)
+const char* bias_row_inverse(const std::vector<int32_t>& bias_rows, int rows, std::vector<int32_t>& e_of) {
+    e_of.assign(rows, -1);
+    for (size_t e = 0; e < bias_rows.size(); ++e) {
+        const int r = bias_rows[e];
+        if (r < 0) continue;
+        if (r >= rows || e_of[r] >= 0) return "internal: bias row table is not one-to-one";
+        e_of[r] = (int32_t)e;
+    }
+    return nullptr;
+}
+
+const char* signal_row_table(const std::vector<int32_t>& bias_rows, const int* elems, int n, std::vector<int32_t>& rows) {
+    const char* no_row = "internal: a signal-term bias element without a gradient row";
+    if (n % 64) return no_row;
+    rows.resize(n);
+    for (int i = 0; i < n; ++i) {
+        rows[i] = bias_rows[elems[i]];
+        if (rows[i] < 0) return no_row;
+        // sig_rows8_kernel: 32 consecutive entries = the rows of one aligned 32-row block
+        if ((rows[i] >> 5) != (rows[i & ~31] >> 5)) return "internal: signal rows not in whole 32-row blocks";
+    }
+    return nullptr;
 }
 
 long build_bwd_plan(int tier, int field, std::vector<int32_t>& plan) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "dfanerf.h"
 #include "dfn_layout.h"
+#include "dfn_plan.h"      // WOp, WItem, WNItem: the tables the weight-gradient launches read
 
 namespace dfn {
 
@@ -34,11 +35,6 @@ struct CompositeBwdArgs {
     long zero_floats;
 };
 
-struct WOp {                    // one weight-gradient GEMM: C[M x N] = dy_T[a_row.., :] * act_T[b_row.., :]^T
-    int a_row, M, b_row, N, c_off;
-    int bias_owner;             // this GEMM also accumulates the row sums of its dy_T rows (bias gradients)
-};
-
 hipError_t launch_mlp_bwd(int tier, int field, const MlpBwdArgs& A, hipStream_t st);
 hipError_t launch_mlp_bwd_bf16(bool torso, const MlpBwdArgs& A, hipStream_t st);     // dfn_bwd_bf16.hip
 void bwd_program_info(int tier, int field, ProgramInfo* out);
@@ -46,28 +42,12 @@ hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st);
 hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st);      // n_fine in {64, 128}
 // Split-K partials: C [ksplit][c_stride] and dbias [ksplit][n_bias], one writer per element and slice (no atomics);
 // launch_reduce_scatter / launch_reduce_bias add the slices in index order (bit-reproducible gradients).
-// f32 tier: two launches per field, both with the operands through LDS (dfn_train.hip) -
-//   wgrad_full_kernel    the 256 x 256 GEMMs (`full_ops_dev`: their indices into ops_dev), one workgroup per (GEMM, slice);
-//   wgrad_narrow_kernel  every other GEMM, one workgroup per WNItem (below), all shapes side by side in ONE launch.
-struct WNItem {                 // slice `ks` of row tiles [m_tile0, m_tile0 + the shape's MT) of GEMM `op` (f32 tier, narrow shapes)
-    int op, ks, m_tile0, shape; // shape: WN_* (dfn_train.hip: the (MT, NT) instantiations of wgrad_lds_part)
-};
-enum WNShape : int { WN_4x4 = 0, WN_4x2, WN_1x8, WN_4x1, WN_2x2, WN_ROWS, WN_COUNT };
-// classification of a GEMM M x N (dy_T rows x act_T rows) for the f32 tier: WN_* and the number of row parts it is cut into
-// (-1: the 256 x 256 shape of wgrad_full_kernel; -2: a shape no kernel is instantiated for)
-DFN_HD constexpr int wn_shape_of(int M, int N) {
-    return (M == 256 && N == 256) ? -1 : (M == 256 && N == 128) ? WN_4x4 : (M == 256 && N == 64) ? WN_4x2 : (M == 32 && N == 256) ? WN_1x8
-         : (M == 256 && N == 32) ? WN_4x1 : (M == 64 && N == 64) ? WN_2x2 : (N == 0 && M > 0 && M % 32 == 0) ? WN_ROWS : -2;
-}
-DFN_HD constexpr int wn_shape_mt(int shape) { return shape == WN_1x8 ? 1 : (shape == WN_2x2 || shape == WN_ROWS) ? 2 : 4; }
+// f32 tier: wgrad_full_kernel + wgrad_narrow_kernel (dfn_plan.h: WNItem)
 hipError_t launch_wgrad(int tier, int field, const WOp* ops_dev, const int* full_ops_dev, int n_full, const WNItem* nitems_dev,
                         int n_nitems, const void* dy_T, const void* act_T, long NP, int ksplit, float* C, long c_stride,
                         const int* e_of, float* dbias, int n_bias, hipStream_t st);
 // bf16 tier: one workgroup per (GEMM, slice of the points), operands through LDS (dfn_wgrad_bf16.hip); order = GEMMs by
 // decreasing size
-struct WItem {                  // one workgroup of the 16-bit tier's weight-gradient launch: slice `ks` of `n` of GEMM `op`
-    int op, ks, n, pad;
-};
 // act_fp4: act_T is MX-fp4 (recorded by the fused training step) / MX-fp8 e4m3 (by the decoder-on-points recorder)
 hipError_t launch_wgrad_bf16(int field, bool act_fp4, const WOp* ops_dev, const WItem* items_dev, int n_items, const void* dy_T,
                              const void* act_T, long NP, float* C, long c_stride, const int* e_of, float* dbias, int n_bias,

@@ -359,7 +359,10 @@ int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples,
  * {a_row, M, b_row, N, c_off, bias_owner}: C[M x N] = dy_T rows [a_row, a_row + M) x act_T rows [b_row, b_row + N)^T summed over the
  * points, stored row-major at c_off of the dense partial array; what == 1 -> map[i] = index into the flat decoder parameter vector
  * the dense element i is added to (-1: structural padding); what == 2 -> bias_rows[e] = dy_T row whose sum over the points is the
- * gradient of bias-blob element e (-1: none).  Returns the number of int32 (out may be NULL to ask), negative on error.
+ * gradient of bias-blob element e (-1: none); what == 3 / 4 -> the workgroups of the 16-bit tier's GEMM launch, in launch order, 3 int32
+ * each {op, ks, n} = slice ks of the n slices of GEMM op (the slices of a GEMM are added in index order: n fixes the bits of its
+ * gradient), for calls of up to 196,608 points (3) and for larger ones (4), split for the compute units of the visible device (256 when
+ * there is none).  Returns the number of int32 (out may be NULL to ask), negative on error.
  * (The backward of Decoder.forward, decoder.py:291-349: one GEMM per nn.Linear the field evaluates.) */
 long dfn_wgrad_plan(int field, int what, int32_t* out, long capacity);
 /* (16-bit tier: dfn_weight_grad / dfn_weight_bias_grad read act_T in the fused step's DEFAULT format, MX-fp4 - 16 bytes per row and

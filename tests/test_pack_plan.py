@@ -275,3 +275,95 @@ def test_flat_param_order_matches_state_dict(states):
     for unused in ("fc_in_listener.weight", "fc_in_torso.weight", "deform_net.out_embed.weight"):
         lo, hi = offs[unused], offs[unused] + st[unused].size
         assert not ((used >= lo) & (used < hi)).any()
+
+
+# ---- the 16-bit tier's weight-gradient split (dfn_plan.cpp: wgrad_split; dfn_wgrad_plan selectors 3 / 4) --------------------
+# The slice count n of a GEMM fixes the order in which its bf16 partial sums are added, hence the bits of the gradient.
+# tests/golden/g16_wgrad_split.json: the splits at 256 compute units as computed by the planner BEFORE it moved into dfn_plan.cpp.
+def _wgrad_plan(lib, field, what):
+    import ctypes
+    n = lib.dfn_wgrad_plan(field, what, None, 0)
+    assert n > 0, lib.dfn_last_error()
+    out = np.zeros(n, np.int32)
+    assert lib.dfn_wgrad_plan(field, what, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n) == n
+    return out
+
+
+def _wgrad_split_fixture():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "g16_wgrad_split.json")) as f:
+        g = json.load(f)
+    assert g["cus"] == 256
+    return g
+
+
+@pytest.mark.parametrize("field", [0, 1, 2])
+def test_wgrad_split_is_the_recorded_one(field):
+    assert not [k for k in os.environ if k.startswith(("DFN_WGRAD_KSPLIT", "DFN_WGRAD_SPARE_CUS"))], "developer overrides are set"
+    g = _wgrad_split_fixture()["balanced"][str(field)]
+    n_ops = _wgrad_plan(_lib.lib, field, 0).size // 6
+    for what, spare in ((3, 32), (4, 8)):
+        items = _wgrad_plan(_lib.lib, field, what)
+        assert items.tolist() == g[str(what)], (field, what)
+        items = items.reshape(-1, 3)
+        # every GEMM of the plan, cut into n <= 32 slices ks = 0 .. n - 1 that follow one another in the launch
+        assert sorted(set(items[:, 0].tolist())) == list(range(n_ops))
+        total = 0
+        for op in range(n_ops):
+            mine = items[items[:, 0] == op]
+            n = int(mine[0, 2])
+            assert 1 <= n <= 32 and mine[:, 1].tolist() == list(range(n)) and (mine[:, 2] == n).all(), (field, what, op)
+            total += n
+        # one workgroup per compute unit at the most, `spare` units left to what runs next to the GEMMs
+        assert total == len(items) <= 256 - spare, (field, what, total)
+
+
+def _wgrad_split_in_child(overrides):
+    """selectors 3 / 4 of all three fields from a fresh process with these DFN_WGRAD_* variables (they are read once per process)"""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, sys, numpy as np, ctypes\n"
+            "from dfanerf import _lib\n"
+            "out = {}\n"
+            "for field in (0, 1, 2):\n"
+            "    out[str(field)] = {}\n"
+            "    for what in (3, 4):\n"
+            "        n = _lib.lib.dfn_wgrad_plan(field, what, None, 0)\n"
+            "        a = np.zeros(max(n, 1), np.int32)\n"
+            "        assert n > 0 and _lib.lib.dfn_wgrad_plan(field, what, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n) == n\n"
+            "        out[str(field)][str(what)] = a.tolist()\n"
+            "print('SPLIT ' + json.dumps(out))\n")
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("DFN_WGRAD_KSPLIT", "DFN_WGRAD_SPARE_CUS"))}
+    env.update(overrides)
+    env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "dfa-nerf_amd")] + env.get("PYTHONPATH", "").split(os.pathsep))
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("SPLIT ")][-1][6:])
+
+
+def _uniform_split_ok(got, want_n):
+    """every GEMM of field f cut into want_n[f] slices, in both splits"""
+    for f in (0, 1, 2):
+        n_ops = _wgrad_plan(_lib.lib, f, 0).size // 6
+        for what in ("3", "4"):
+            items = np.array(got[str(f)][what]).reshape(-1, 3)
+            assert len(items) == want_n[f] * n_ops and (items[:, 2] == want_n[f]).all(), (f, what)
+            for op in range(n_ops):
+                assert items[items[:, 0] == op][:, 1].tolist() == list(range(want_n[f])), (f, what, op)
+
+
+def test_wgrad_split_uniform_override():
+    """DFN_WGRAD_KSPLIT (developer override): 16 slices for every GEMM - the recorded lists"""
+    got = _wgrad_split_in_child({"DFN_WGRAD_KSPLIT": "16"})
+    assert got == _wgrad_split_fixture()["ksplit16"]
+    _uniform_split_ok(got, {0: 16, 1: 16, 2: 16})
+
+
+def test_wgrad_split_override_precedence_and_range():
+    """The field's own variable goes ahead of the general one: _H for the head; _T for the torso and - for the item split, as it
+    always has - the listener.  A value outside 1 .. 32 is ignored: the balanced split."""
+    _uniform_split_ok(_wgrad_split_in_child({"DFN_WGRAD_KSPLIT_T": "12", "DFN_WGRAD_KSPLIT": "16"}), {0: 16, 1: 12, 2: 12})
+    # (a field variable that is set hides the general one even when its own value is out of range: _H = 0 -> balanced)
+    assert _wgrad_split_in_child({"DFN_WGRAD_KSPLIT": "33", "DFN_WGRAD_KSPLIT_H": "0"}) == _wgrad_split_fixture()["balanced"]
