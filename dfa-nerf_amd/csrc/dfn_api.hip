@@ -231,6 +231,19 @@ int wgrad_splits(WgradEntry& w, int field) {
 
 // the small rules of the entry points, stated once
 bool coarse_ok(int n) { return n == 32 || n == 64 || n == 128; }     // --N_samples (MAIN:612-619): 32, 64 or 128 coarse samples
+// the sample counts of a FORWARD launch (render_kernel): n_fine = 0, 32, 64 or 128; with a fine pass the sampler is a 64-lane wave
+// program with one coarse sample per lane, so n_coarse = 32 or 64, and n_fine <= 2 n_coarse (128 fine samples need 64 coarse ones).
+// The hierarchical BACKWARD (dfn_composite_bwd_hier) keeps 64 + 64 | 128: its own check.
+int counts_ok(int n_coarse, int n_fine, const char* who) {
+    if (!coarse_ok(n_coarse)) return fail(DFN_E_ARG, std::string(who) + ": n_coarse must be 32, 64 or 128");
+    if (n_fine != 0 && n_fine != 32 && n_fine != 64 && n_fine != 128)
+        return fail(DFN_E_ARG, std::string(who) + ": n_fine must be 0, 32, 64 or 128");
+    // (128 fine samples first: with them the one coarse count is 64, whatever else was asked for)
+    if (n_fine == 128 && n_coarse != 64) return fail(DFN_E_ARG, std::string(who) + ": n_fine = 128 needs n_coarse = 64 (n_fine <= 2 n_coarse <= 128)");
+    if (n_fine != 0 && n_coarse != 32 && n_coarse != 64)
+        return fail(DFN_E_ARG, std::string(who) + ": the hierarchical mode (n_fine > 0) needs n_coarse = 32 or 64");
+    return DFN_OK;
+}
 int smo_ok(int smo_size, const char* who) {
     if (smo_size < 0 || smo_size > 8 || (smo_size & 1)) return fail(DFN_E_ARG, std::string(who) + ": smo_size must be 0, 2, 4, 6 or 8");
     return DFN_OK;
@@ -399,11 +412,7 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
     if (!tier_ok(tier) || !frame || !packed_head || !bias_head || !rgb_head)
         return fail(DFN_E_ARG, "dfn_render_fwd: bad argument");
     const DfnFrame& F = *frame;
-    // the hierarchical sampler (a 64-lane wave program) needs 64 coarse samples
-    if (!coarse_ok(F.n_coarse)) return fail(DFN_E_ARG, "dfn_render_fwd: n_coarse must be 32, 64 or 128");
-    if (F.n_fine != 0 && F.n_fine != 64 && F.n_fine != 128)
-        return fail(DFN_E_ARG, "dfn_render_fwd: n_fine must be 0, 64 or 128");
-    if (F.n_fine != 0 && F.n_coarse != 64) return fail(DFN_E_ARG, "dfn_render_fwd: the hierarchical mode (n_fine > 0) needs n_coarse = 64");
+    if (counts_ok(F.n_coarse, F.n_fine, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
     if (F.fields != 1 && F.fields != 2) return fail(DFN_E_ARG, "dfn_render_fwd: fields must be 1 or 2");
     if (F.fields == 2 && (!packed_torso || !bias_torso || !rgb_com))
         return fail(DFN_E_ARG, "dfn_render_fwd: torso inputs / rgb_com missing for fields == 2");
@@ -602,8 +611,10 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
     if (!hier && (!coarse_ok(F.n_coarse) || F.n_fine != 0 || F.fields != 2))
         return fail(DFN_E_ARG, "dfn_train_fwd: the training step is coarse-only (64 samples), two fields (MAIN:855-899); "
                                "dfn_train_fwd_hier is the hierarchical variant");
-    if (hier && (F.n_coarse != 64 || (F.n_fine != 64 && F.n_fine != 128) || F.fields != 2))
-        return fail(DFN_E_ARG, "dfn_train_fwd_hier: 64 coarse + 64 or 128 fine samples, two fields");
+    // (the forward records at every pair the renderer takes - the f16 guards calibrate through it; the backward is 64 + 64 | 128)
+    if (hier && (F.n_fine == 0 || F.fields != 2))
+        return fail(DFN_E_ARG, "dfn_train_fwd_hier: n_fine > 0 (dfn_train_fwd is the coarse-only step), two fields");
+    if (hier && counts_ok(F.n_coarse, F.n_fine, who) != DFN_OK) return DFN_E_ARG;
     if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, std::string(who) + ": no background given");
     if (F.ray_count <= 0) return DFN_OK;
     const long NP = (long)F.ray_count * (F.n_coarse + F.n_fine);

@@ -4,9 +4,9 @@
 // aux / rays switches.
 //
 // One wavefront = one ray.  A workgroup of W waves (8 in the bf16 tier, 4 in the f32 tier) walks W rays
-// through: ray generation -> 64 coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
+// through: ray generation -> n_coarse coarse samples -> [head MLP (+ torso MLP)] on 32-sample tiles ->
 // online alpha compositing -> (optional) inverse-CDF fine sampling, rank merge -> the same MLPs on the
-// merged 64+n_fine samples -> compositing -> 12 (or 24) bytes of RGB per ray.  Nothing but the packed
+// merged n_coarse+n_fine samples -> compositing -> 12 (or 24) bytes of RGB per ray.  Nothing but the packed
 // weight stream, the per-frame bias blob and one background pixel per ray is read from memory.
 //
 // Reference semantics (paths under /root/reference/NeRFs/DFANeRF/):
@@ -111,7 +111,7 @@ template <int TIER, bool TWO = false> struct KernelLds {
     static constexpr int BIAS_T = BIAS_H + P::H_NBIAS * 4;
     static constexpr int SCRATCH = BIAS_T + P::T_NBIAS * 4;
     // per wave (floats): zall[192] | M[4][192] | rank8[128 bytes] | state[32]
-    //   zall   sample depths: the 64 coarse z, then the merged, sorted 64 + n_fine
+    //   zall   sample depths: the coarse z (up to 128; 32 or 64 before a fine pass), then the merged, sorted n_coarse + n_fine
     //   M      per merged sample (sigma, r, g, b) of the field set being composited; while the coarse pass and
     //          sample_pdf run its first 256 floats hold tmp[64] cdf[64] zf[128]
     //   rank8  merged rank of fine sample j (u8)
@@ -128,12 +128,12 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // ================================================================================================
 // Frame renderer
 // ================================================================================================
-// Pass order of one ray (= one wave): coarse tiles 0,1 (head, then torso when two fields are rendered), the
+// Pass order of one ray (= one wave): the coarse tiles (head, then torso when two fields are rendered), the
 // fine sampler, then the decoder on the n_fine NEW points only - there is one network (SURVEY.md 8(a) row H,
-// step 4), so its outputs at the 64 coarse points are kept from the coarse pass instead of being evaluated a
+// step 4), so its outputs at the coarse points are kept from the coarse pass instead of being evaluated a
 // second time: head on the fine tiles, compositing of the head image over the merged samples, torso on the fine
 // tiles, compositing of the two-field image.  Every sample's (sigma, rgb) is bit-identical to what a pass over
-// all 64 + n_fine merged points gives (an MFMA column depends on its own point only).
+// all n_coarse + n_fine merged points gives (an MFMA column depends on its own point only).
 // TRAIN: 0 = inference; 1 = the training forward of the reference's step (MAIN:855-899: coarse samples only, recorder on);
 // 2 = the hierarchical training forward (row H under autograd: the fine depths are constants - no gradient through
 // sample_pdf, as in the NeRF lineage - and the loss sees the merged 64 + n_fine samples: every point is evaluated ONCE with
@@ -203,9 +203,10 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     const int NF = TRAIN == 1 ? 0 : F.n_fine;     // TRAIN == 1: the training forward is the reference's coarse renderer
     const bool hier = NF > 0;
     const int KF = NF / 32;                        // fine tiles
-    // coarse samples per ray (--N_samples, MAIN:612-619): 64 in the scripts; 32 and 128 too when there is no fine pass (round 6:
-    // the coarse loop walks NC / 32 tiles; the hierarchical sampler is a 64-lane wave program and keeps NC = 64, dfn_api.hip)
-    const int NC = hier ? 64 : F.n_coarse;
+    // coarse samples per ray (--N_samples, MAIN:612-619): 64 in the scripts; 32 and 128 too when there is no fine pass.  The coarse
+    // loop walks NC / 32 tiles.  The hierarchical sampler is a 64-lane wave program, one coarse sample per lane: NC = 32 or 64 there,
+    // with lanes >= NC idle, and n_fine = 32, 64 or 128 (the pairs the entry points accept: counts_ok, dfn_api.hip)
+    const int NC = F.n_coarse;
     const int S = NC + NF;
 
     Stream s;
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     s.nslab0 = A.nslab[0];
     s.nslab1 = A.nslab[1];
     // coarse: H T per coarse tile (NC / 32 of them: H T H T for the scripts' 64); fine: KF x H, then KF x T
-    const int KC = (F.n_fine > 0 && TRAIN != 1) ? 2 : F.n_coarse / 32;
+    const int KC = NC / 32;
     s.sched = two ? ((0xAAu & ((1u << (2 * KC)) - 1u)) | (((1u << KF) - 1u) << (2 * KC + KF))) : 0u;
 #ifdef DFN_TIMING
     s.t_wait = s.t_bar = s.t_issue = 0;
@@ -396,9 +397,9 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 #pragma unroll
             for (int k = 0; k < 3; ++k) p[k] = add_(st[RS_OH + k], mul_(st[RS_DH + k], z));
             if constexpr (TRAIN != 0) {      // idle waves (ray >= ray_count) record into the last ray's slots: same values
-                // tiles of a ray in evaluation order: coarse 0, 1, then the fine tiles
+                // tiles of a ray in evaluation order: the NC / 32 coarse tiles, then the fine tiles
                 const long rr = valid ? r_raw : F.ray_count - 1;
-                ctx.rec = {A.act_T[0], A.masks[0], RecMap::H_ROWS, rr * (S / 32) + (phase == PH_COARSE ? tile : 2 + tile),
+                ctx.rec = {A.act_T[0], A.masks[0], RecMap::H_ROWS, rr * (S / 32) + (phase == PH_COARSE ? tile : KC + tile),
                            RecMap::H_MDWORDS};
             }
 #ifdef DFN_TIMING
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             for (int k = 0; k < 3; ++k) p[k] = add_(st[RS_OT + k], mul_(st[RS_DT + k], z));
             if constexpr (TRAIN != 0) {
                 const long rr = valid ? r_raw : F.ray_count - 1;
-                ctx.rec = {A.act_T[1], A.masks[1], RecMap::S_ROWS, rr * (S / 32) + (phase == PH_COARSE ? tile : 2 + tile),
+                ctx.rec = {A.act_T[1], A.masks[1], RecMap::S_ROWS, rr * (S / 32) + (phase == PH_COARSE ? tile : KC + tile),
                            RecMap::S_MDWORDS};
             }
             b = mlp_torso<TIER, HT>(p, dref_t, bias_t, s, ctx);
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 
         if (phase == PH_COARSE) {
             const int si = idx;
-            if (TRAIN != 0 && valid && lane < 32) {      // raw outputs, evaluation order: [ray][64 coarse | n_fine fine][8]
+            if (TRAIN != 0 && valid && lane < 32) {      // raw outputs, evaluation order: [ray][NC coarse | n_fine fine][8]
                 float* so = A.samples_out + ((size_t)r_raw * S + si) * 8;
                 so[0] = a.sigma; so[1] = a.r; so[2] = a.g; so[3] = a.b;
                 so[4] = b.sigma; so[5] = b.r; so[6] = b.g; so[7] = b.b;
@@ -476,39 +477,41 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 #endif
             // ---- sample_pdf(z_mid, weights[1:-1], n_fine, det=True), run_nerf_helpers.py:537-581 ----
             wave_lds_fence();
-            const float wp = (lane >= 1 && lane <= 62) ? add_(tmp[lane], 1e-5f) : 0.f;
+            const float wp = (lane >= 1 && lane <= NC - 2) ? add_(tmp[lane], 1e-5f) : 0.f;
             // sum(weights + 1e-5) in the library's documented order (sample_pdf_kernel, oracle wave_sum64): element k
-            // (= coarse weight k + 1) sits in lane k, lanes combine by a butterfly at XOR distances 32, 16, ..., 1
+            // (= coarse weight k + 1) sits in lane k, lanes combine by a butterfly at XOR distances 32, 16, ..., 1 (the lanes past the
+            // NC - 2 elements hold 0.f: the zeros wave_sum64 pads with)
             float Ssum = __shfl(wp, (lane + 1) & 63);
 #pragma unroll
             for (int dlt = 32; dlt >= 1; dlt >>= 1) Ssum += __shfl_xor(Ssum, dlt);
             const float pdf = div_(wp, Ssum);
-            const float zmid = (lane < 63) ? mul_(0.5f, add_(zc[lane + 1], zc[lane])) : 0.f;
+            const float zmid = (lane < NC - 1) ? mul_(0.5f, add_(zc[lane + 1], zc[lane])) : 0.f;
             // torch.cumsum as the reference's CPU path computes it: accumulator in DOUBLE (at::acc_type<float, false>),
             // every prefix rounded to f32 on output.  Here as a 6-step wave scan instead of the 62-step sequential loop,
-            // bit-identical to it: every pdf entry is an f32 in [1e-5 / 1.0007, 1] (compositing weights are >= 0 and sum
+            // bit-identical to it (for any NC): every pdf entry is an f32 in [1e-5 / 1.0007, 1] (compositing weights are >= 0 and sum
             // to <= 1) and every prefix is < 2, i.e. a multiple of 2^-40 below 2 = 41 bits: double additions of them are
             // EXACT in any order.  (The stand-alone sample_pdf_kernel takes arbitrary weights and keeps the loop.)
-            double c = (double)pdf;          // lanes 0 and 63 hold 0
+            double c = (double)pdf;          // lanes 0 and >= NC - 1 hold 0
 #pragma unroll
             for (int dlt = 1; dlt < 64; dlt <<= 1) {
                 const double up = __shfl_up(c, dlt);
                 if (lane >= dlt) c += up;
             }
-            cdf[lane] = (lane <= 62) ? (float)c : 3.0e38f;
+            cdf[lane] = (lane <= NC - 2) ? (float)c : 3.0e38f;
             wave_lds_fence();
             tmp[lane] = zmid;                // bins
             wave_lds_fence();
-            for (int m = 0; m < NF / 64; ++m) {
+            for (int m = 0; m < (NF + 63) / 64; ++m) {
                 const int j = lane + 64 * m;
+                if (j >= NF) continue;       // (NF = 32: half the wave owns a fine sample)
                 const float u = linspace01(j, NF);
-                int inds = 0;                // searchsorted(cdf[0..62], u, right=True)
+                int inds = 0;                // searchsorted(cdf[0..NC-2], u, right=True)
 #pragma unroll
                 for (int stp = 32; stp >= 1; stp >>= 1) {
                     const int t = inds + stp;
-                    if (t <= 63 && cdf[t - 1] <= u) inds = t;
+                    if (t <= NC - 1 && cdf[t - 1] <= u) inds = t;
                 }
-                const int below = max(inds - 1, 0), above = min(inds, 62);
+                const int below = max(inds - 1, 0), above = min(inds, NC - 2);
                 const float cb = cdf[below], ca = cdf[above];
                 const float bb = tmp[below], ba = tmp[above];
                 float den = sub_(ca, cb);
@@ -518,18 +521,21 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             }
             wave_lds_fence();
             // ---- z_all = sort(cat(z, z_fine)): ranks by counting, no sortedness assumption on z_fine ----
-            const float myc = zc[lane];
+            // lane < NC owns coarse sample `lane`, lane + 64 m < NF owns fine sample lane + 64 m: the others compute on zeros and
+            // store nothing
+            const bool own_c = lane < NC;
+            const float myc = own_c ? zc[lane] : 0.f;
             int rank_f[3] = {0, 0, 0};
             float myf[3] = {0, 0, 0};
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
-                if (m < NF / 64) {
+                if (lane + 64 * m < NF) {
                     myf[m] = zf[lane + 64 * m];
                     int cnt = 0;             // coarse values <= mine (zc strictly increasing)
 #pragma unroll
                     for (int stp = 64; stp >= 1; stp >>= 1) {
                         const int t = cnt + stp;
-                        if (t <= 64 && zc[t - 1] <= myf[m]) cnt = t;
+                        if (t <= NC && zc[t - 1] <= myf[m]) cnt = t;
                     }
                     rank_f[m] = cnt;
                 }
@@ -540,11 +546,10 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             // this section used to take per ray).  Checked per ray; the counting loop stays as the general path.
             bool sorted_f = true;
 #pragma unroll
-            for (int m = 0; m < 3; ++m)
-                if (m < NF / 64) {
-                    const int j = lane + 64 * m;
-                    if (j + 1 < NF && zf[j + 1] < myf[m]) sorted_f = false;
-                }
+            for (int m = 0; m < 3; ++m) {
+                const int j = lane + 64 * m;
+                if (j + 1 < NF && zf[j + 1] < myf[m]) sorted_f = false;
+            }
             if (__builtin_amdgcn_ballot_w64(!sorted_f) == 0) {
 #pragma unroll
                 for (int m = 0; m < 3; ++m) rank_f[m] += lane + 64 * m;       // fine samples before mine: exactly j
@@ -570,22 +575,24 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 #pragma unroll
             for (int q = 0; q < 4; ++q) keep_h[q] = park_h[q * 64 + lane];
             wave_lds_fence();                // every read of zc / zf / tmp / cdf / park_h is done: the areas are reused
-            zall[rank_c] = myc;
+            if (own_c) zall[rank_c] = myc;
 #pragma unroll
             for (int m = 0; m < 3; ++m)
-                if (m < NF / 64) {
+                if (lane + 64 * m < NF) {
                     zall[rank_f[m]] = myf[m];
                     rank8[lane + 64 * m] = (unsigned char)rank_f[m];
                 }
+            if (own_c) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) M[q * L::M_STRIDE + rank_c] = keep_h[q];
+                for (int q = 0; q < 4; ++q) M[q * L::M_STRIDE + rank_c] = keep_h[q];
+            }
             if constexpr (TRAIN == 2) {      // merged rank of every evaluated point, for the compositing backward
                 if (valid) {
                     unsigned char* ro = A.ranks_out + (size_t)r_raw * S;
-                    ro[lane] = (unsigned char)rank_c;
+                    if (own_c) ro[lane] = (unsigned char)rank_c;
 #pragma unroll
                     for (int m = 0; m < 3; ++m)
-                        if (m < NF / 64) ro[64 + lane + 64 * m] = (unsigned char)rank_f[m];
+                        if (lane + 64 * m < NF) ro[NC + lane + 64 * m] = (unsigned char)rank_f[m];
                 }
             }
             if (lane == 0) {                 // the merged compositing starts from scratch
@@ -602,7 +609,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             tile = 0;
         } else if (phase == PH_FINE_H) {
             if (TRAIN == 2 && valid && lane < 32) {
-                float* so = A.samples_out + ((size_t)r_raw * S + 64 + idx) * 8;
+                float* so = A.samples_out + ((size_t)r_raw * S + NC + idx) * 8;
                 so[0] = a.sigma; so[1] = a.r; so[2] = a.g; so[3] = a.b;
             }
             if (lane < 32) {
@@ -619,7 +626,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             tile = 0;
         } else {
             if (TRAIN == 2 && valid && lane < 32) {
-                float* so = A.samples_out + ((size_t)r_raw * S + 64 + idx) * 8;
+                float* so = A.samples_out + ((size_t)r_raw * S + NC + idx) * 8;
                 so[4] = b.sigma; so[5] = b.r; so[6] = b.g; so[7] = b.b;
             }
             if (lane < 32) {                 // the sample's head outputs are in M: replace them by the two-field mix
@@ -637,8 +644,10 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
                 M[3 * L::M_STRIDE + ri] = fm[2];
             }
             if (++tile < KF) continue;
+            if (lane < NC) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) M[q * L::M_STRIDE + rank_c] = keepc[q * 64 + lane];
+                for (int q = 0; q < 4; ++q) M[q * L::M_STRIDE + rank_c] = keepc[q * 64 + lane];
+            }
             wave_lds_fence();
             composite_merged(false, A.w_com);
             break;

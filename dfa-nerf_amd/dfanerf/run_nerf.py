@@ -136,7 +136,8 @@ _EXTRA_HELP = {
     "hip_train_act": "16-bit training tier: format of the recorded layer inputs that feed the weight gradients: fp4 (MX-fp4 "
                      "e2m1, default: half the bytes; a weight gradient sums >= 131,072 points and the rounding averages out - "
                      "tests/test_gpu_convergence.py trains to convergence in both) | e4m3 (MX-fp8, +5 % step time)",
-    "hierarchical": "64 + N_importance samples per ray (coarse pass -> sample_pdf -> the same decoder on the merged depths)",
+    "hierarchical": "N_samples + N_importance samples per ray (coarse pass -> sample_pdf -> the same decoder on the merged depths): "
+                    "64 + 64 | 128; with --render_person also 32 + 32, 32 + 64 and 64 + 32 (the speed / quality knob of a render)",
     "image_ext": "file type of the rendered frames (jpg as upstream; png keeps the kernel's uint8 output losslessly)",
     "save_alpha": "write, next to every rendered frame <name>.<ext>, <name>_alpha.png: the opacity of the rendered foreground (alpha "
                   "matte of the head in render_head/, of head + torso in render_com/; background plane excluded) as 8-bit greyscale, "
@@ -429,7 +430,7 @@ class FrameRenderer:
                                               self.args.concate_bg))
         with torch.no_grad():
             pk.f16_bounds = f16guard.activation_bounds(pk.flat, frs, sh, stt, self.zs, self.za, self.bg, n_rays=n_rays,
-                                                       n_fine=self.n_fine if self.args.N_samples == 64 else 0, z_dim=pk.z_dim)
+                                                       n_fine=self.n_fine, z_dim=pk.z_dim)
         top = f16guard.check(pk.f16_bounds, pk.f16_weight_max, tier=self.tier)
         print(f"[dfanerf] {self.tier} tier: calibrated on {len(pick)} frames x {n_rays} rays in the exact tier: max |activation| "
               f"{top:.4g}, max |parameter| {pk.f16_weight_max:.4g} (half precision holds {f16guard.F16_MAX:.0f}; margin x{f16guard.MARGIN:g})")
@@ -931,10 +932,16 @@ def check_supported(args):
     # nothing ever steps - deform(p) + p = p exactly)
     if args.N_samples not in (32, 64, 128):
         bad.append(f"--N_samples {args.N_samples} (supported: 32, 64, 128)")
-    if getattr(args, "hierarchical", False) and args.N_samples != 64:
-        bad.append(f"--hierarchical with --N_samples {args.N_samples} (the fused fine sampler works on 64 coarse samples)")
-    if getattr(args, "hierarchical", False) and args.N_importance not in (64, 128):
-        bad.append(f"--hierarchical with --N_importance {args.N_importance} (supported: 64, 128)")
+    if getattr(args, "hierarchical", False):
+        # the renderer's rule (include/dfanerf.h): one coarse sample per lane of the fine sampler's wave, N_importance <= 2 N_samples
+        if args.N_samples not in (32, 64):
+            bad.append(f"--hierarchical with --N_samples {args.N_samples} (the fused fine sampler works on 32 or 64 coarse samples)")
+        elif args.N_importance not in (32, 64, 128) or args.N_importance > 2 * args.N_samples:
+            bad.append(f"--hierarchical with --N_samples {args.N_samples} --N_importance {args.N_importance} (supported: N_importance "
+                       "32, 64 or 128, at most 2 x N_samples)")
+        elif not args.render_person and (args.N_samples != 64 or args.N_importance not in (64, 128)):
+            bad.append(f"--hierarchical with --N_samples {args.N_samples} --N_importance {args.N_importance} in a training run (the "
+                       "hierarchical training step is 64 + 64 | 128; the other counts render only: --render_person)")
     if args.n_object < 1:
         bad.append(f"--n_object {args.n_object}")
     # (--n_object > 1, the flag's default: accepted like upstream - and like upstream the run stops in the setup loop over the

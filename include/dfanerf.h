@@ -86,8 +86,12 @@ typedef struct DfnFrame {
     float last_dist;       /* --last_dist, MAIN:171 */
     int ray_begin;         /* first ray (y*W+x) rendered when pix_index == NULL */
     int ray_count;         /* number of rays rendered by this call */
-    int n_coarse;          /* --N_samples (MAIN:612-619): 32, 64 or 128; 64 when n_fine > 0 */
-    int n_fine;            /* 0 (live reference renderer) or 64/128 */
+    int n_coarse;          /* --N_samples (MAIN:612-619): 32, 64 or 128; 32 or 64 when n_fine > 0 */
+    int n_fine;            /* 0 (live reference renderer) or 32 / 64 / 128; 128 needs n_coarse = 64.
+                            * The forward entry points (dfn_render_fwd and its u8 / aux / rays / DFN_WIDTH_128 forms,
+                            * dfn_train_fwd_hier[_loss]) take the pairs 32+32, 32+64, 64+32, 64+64, 64+128 and refuse every
+                            * other (n_fine = 96; 96 or 128 coarse samples with a fine pass; 32+128) with DFN_E_ARG before
+                            * any device work.  dfn_composite_bwd_hier - the hierarchical training STEP - is 64 + 64 | 128 */
     int fields;            /* 1 = head only, 2 = head + torso composite (MAIN:681-709) */
     int concate_bg;        /* --concate_bg, MAIN:669-671, 678-679, 692-694 */
 } DfnFrame;
@@ -223,7 +227,7 @@ int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_he
  *   bg_f32 / bg_u8  [ray_count, 3]: row r is the background of RAY r (there is no pixel id; give one of the two)
  * Frame fields used: ray_count, n_coarse, n_fine, fields, concate_bg, last_dist, and z_near / z_far when bounds == NULL.  Frame
  * fields IGNORED: H, W, focal, cx, cy, pose, pose_body, ray_begin (they may hold anything).
- * Outputs, sample-count / fields / adjacent-bias checks: dfn_render_fwd's (the hierarchical mode needs n_coarse = 64).  Given the
+ * Outputs, sample-count / fields / adjacent-bias checks: dfn_render_fwd's (the hierarchical mode takes DfnFrame's pairs: n_coarse = 32 or 64, n_fine <= 2 n_coarse).  Given the
  * rays dfn_get_rays makes for a pose, bg rows gathered at the same pixels and no bounds (or bounds filled with z_near, z_far), every
  * output equals dfn_render_fwd's bit for bit: the kernels differ in where the ray comes from, nothing else.
  * Tiers DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3, with or without DFN_WIDTH_128.  DFN_E_ARG with a message, before any device
@@ -282,13 +286,16 @@ int dfn_train_fwd(int tier, const DfnFrame* frame, const void* packed_head, cons
                   const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                   uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, void* stream);
 /* The hierarchical variant of the training forward (SURVEY.md 8(a) row H under autograd; 8(d) "report also the hierarchical
- * variant"; the composition of MAIN:119-124 `N_importance` + HELP:537-581 sample_pdf in the NeRF lineage): frame->n_fine = 64
- * or 128.  The fine depths are constants (sample_pdf's output is detached, as the lineage does), the loss sees the images
- * composited over the merged 64 + n_fine samples.  Every point is evaluated once with the recorder on, in EVALUATION order
- * (per ray: the 64 coarse points, then the n_fine fine ones): NP = (64 + n_fine) * ray_count for samples / act / masks /
- * dy_T.  Two more outputs feed dfn_composite_bwd_hier: z_all f32 [ray_count][64 + n_fine] (merged, sorted depths) and
- * ranks u8 [ray_count][64 + n_fine] (merged rank of evaluated point i).  dfn_mlp_bwd / dfn_weight_bias_grad / ... are
- * the same calls with that NP. */
+ * variant"; the composition of MAIN:119-124 `N_importance` + HELP:537-581 sample_pdf in the NeRF lineage): frame->n_fine > 0.
+ * The fine depths are constants (sample_pdf's output is detached, as the lineage does), the loss sees the images
+ * composited over the merged n_coarse + n_fine samples.  Every point is evaluated once with the recorder on, in EVALUATION order
+ * (per ray: the n_coarse coarse points, then the n_fine fine ones): NP = (n_coarse + n_fine) * ray_count for samples / act /
+ * masks / dy_T.  Two more outputs feed dfn_composite_bwd_hier: z_all f32 [ray_count][n_coarse + n_fine] (merged, sorted depths)
+ * and ranks u8 [ray_count][n_coarse + n_fine] (merged rank of evaluated point i).  dfn_mlp_bwd / dfn_weight_bias_grad / ... are
+ * the same calls with that NP.
+ * Sample counts: the FORWARD (this call and its _loss form) takes every pair dfn_render_fwd takes (DfnFrame: 32+32, 32+64, 64+32,
+ * 64+64, 64+128) - the f16 tier's range guard calibrates through it at the render's own counts.  The BACKWARD
+ * (dfn_composite_bwd_hier) takes 64 + 64 | 128 only: training at the other pairs is not built. */
 int dfn_train_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                        const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                        const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
