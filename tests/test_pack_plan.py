@@ -171,12 +171,20 @@ def flat_params(state):
     return np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in state.values()])
 
 
-def emulate(tier, field, st, pe, pev, sig, zs, za):
+def emulate(tier, field, st, pe, pev, sig, zs, za, rnd=None, reader=None):
     """numpy restatement of mlp_head / mlp_torso (dfn_mlp.h) driven by the packed stream.
-    pe [N,60], pev [N,24] -> feat [N,3], sigma [N].  Biases folded like dfn_misc.hip:fold_kernel."""
+    pe [N,60], pev [N,24] -> feat [N,3], sigma [N].  Biases folded like dfn_misc.hip:fold_kernel.
+    rnd (optional): the operand rounding of a 16-bit tier, x -> x rounded to the tier's type.  Every GEMM operand goes through it:
+    the weights, and each layer's activations after bias / ReLU / skip add (f32 in the kernels: acc_to_vec, acc_relu_add, the
+    torso's deform(p) + p) - the biases, sigma and the colour logits stay unrounded.  The caller hands in pe / pev already rounded.
+    reader (optional): flat parameters -> an object with Reader's layer / layer_skip / group (tests/blend_scene.DenseReader)."""
     P = {k: np.asarray(v, np.float64) for k, v in st.items()}
-    rd = Reader(tier, field, flat_params(st).astype(np.float64))
+    flat = flat_params(st).astype(np.float64)
+    if rnd is not None:
+        flat = getattr(rnd, "weights", rnd)(flat)      # (a hook may carry another rounding for the weights than for the activations)
+    rd = Reader(tier, field, flat) if reader is None else reader(flat)
     u = UPT[tier]
+    q = (lambda x: x) if rnd is None else rnd
     relu = lambda x: np.maximum(x, 0)
     N = pe.shape[0]
     pe64 = np.zeros((N, 64)); pe64[:, :60] = pe
@@ -191,47 +199,48 @@ def emulate(tier, field, st, pe, pev, sig, zs, za):
         if field == 0:
             b_in = b_in + P[nm[0] + ".weight"][:, 60:] @ sig
             b_sk = b_sk + P[nm[1] + ".weight"][:, 60:] @ sig
-        act = relu(pe64 @ rd.layer(8, 2 * u, 64).T + b_in)
+        act = q(relu(pe64 @ rd.layer(8, 2 * u, 64).T + b_in))
         pvec, kup, nps = pe64, 2 * u, 64
     else:
         w = lambda n: P[f"deform_net.{n}.weight"]
         b = lambda n: P[f"deform_net.{n}.bias"]
-        ve = relu(pe64 @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.0") + w("blocks_embed.0")[:, 60:] @ sig)
-        vs = relu(pe64 @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.0") + w("blocks_signal.0")[:, 60:] @ sig)
-        ve = relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.1"))
-        vs = relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.1"))
-        ve = relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.2"))
-        vs = relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.2"))
+        ve = q(relu(pe64 @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.0") + w("blocks_embed.0")[:, 60:] @ sig))
+        vs = q(relu(pe64 @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.0") + w("blocks_signal.0")[:, 60:] @ sig))
+        ve = q(relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.1")))
+        vs = q(relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.1")))
+        ve = q(relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.2")))
+        vs = q(relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.2")))
         w3, wsk = rd.layer_skip(2, 2 * u, 64, 2 * u, 64)
-        ve = relu(ve @ w3.T + b("blocks_embed.3")) + b("fc_embed_skips.0") + pe64 @ wsk.T
-        vs = relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.3")) + b("fc_signal_skips.0") + \
-            w("fc_signal_skips.0") @ sig
-        ve = relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.4"))
-        vs = relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.4"))
+        ve = q(relu(ve @ w3.T + b("blocks_embed.3")) + b("fc_embed_skips.0") + pe64 @ wsk.T)
+        vs = q(relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.3")) + b("fc_signal_skips.0") +
+               w("fc_signal_skips.0") @ sig)
+        ve = q(relu(ve @ rd.layer(2, 2 * u, 64).T + b("blocks_embed.4")))
+        vs = q(relu(vs @ rd.layer(2, 2 * u, 64).T + b("blocks_signal.4")))
         eo = ve @ rd.layer(2, 2 * u, 64).T + np.pad(b("out_embed"), (0, 4))
         so = vs @ rd.layer(2, 2 * u, 64).T + np.pad(b("out_signal") + sig, (0, 22))
-        pd = np.concatenate([eo + pe64, so], 1)
-        act = relu(pd @ rd.layer(8, 4 * u, 128).T + P["fc_in_torso.bias"] + fcz)
+        pd = q(np.concatenate([eo + pe64, so], 1))
+        act = q(relu(pd @ rd.layer(8, 4 * u, 128).T + P["fc_in_torso.bias"] + fcz))
         b_sk = P["fc_p_skips_torso.0.bias"] + fczs
         pvec, kup, nps = pd, 4 * u, 128
     for l in range(3):
-        act = relu(act @ rd.layer(8, 8 * u, 256).T + P[f"blocks.{l}.bias"])
+        act = q(relu(act @ rd.layer(8, 8 * u, 256).T + P[f"blocks.{l}.bias"]))
     w4, wsk = rd.layer_skip(8, 8 * u, 256, kup, nps)
-    act = relu(act @ w4.T + P["blocks.3.bias"]) + b_sk + pvec @ wsk.T
+    act = q(relu(act @ w4.T + P["blocks.3.bias"]) + b_sk + pvec @ wsk.T)
     for l in range(4, 7):
-        act = relu(act @ rd.layer(8, 8 * u, 256).T + P[f"blocks.{l}.bias"])
+        act = q(relu(act @ rd.layer(8, 8 * u, 256).T + P[f"blocks.{l}.bias"]))
     rows = []
     for tg in range(4):
         rows.append(act @ rd.group(2, 8 * u, 256).T + v32 @ rd.group(2, u, 32).T)
-    hid = relu(np.concatenate(rows, 1) + P["feat_view.bias"] + fczv + P["fc_view.bias"])
+    hid = q(relu(np.concatenate(rows, 1) + P["feat_view.bias"] + fczv + P["fc_view.bias"]))
     sg = act @ rd.group(1, 8 * u, 256).T + v32 @ rd.group(1, u, 32).T
     sigma = sg[:, 0] + P["sigma_out.bias"][0]
     assert np.abs(sg[:, 1:]).max() == 0          # rows 1..31 of the sigma tile are structural zeros
     out = hid @ rd.group(1, 8 * u, 256).T
     assert np.abs(out[:, 3:]).max() == 0
     feat = 1 / (1 + np.exp(-(out[:, :3] + P["feat_out.bias"])))
-    frag_elems = 64 * E[tier]
-    assert rd.pos % frag_elems == 0 and (rd.plan[rd.pos:] == -1).all()     # only slab padding remains
+    if reader is None:
+        frag_elems = 64 * E[tier]
+        assert rd.pos % frag_elems == 0 and (rd.plan[rd.pos:] == -1).all()     # only slab padding remains
     return feat, sigma
 
 
