@@ -1171,6 +1171,24 @@ int dfn_debug_clock_probe(uint64_t* probe) {
     return DFN_OK;
 }
 
+long dfn_mfma16_map(int32_t* out, long capacity) {
+    constexpr long N = 1024;
+    if (out) {
+        if (capacity < N) return fail(DFN_E_SIZE, "dfn_mfma16_map: capacity too small");
+        for (int lane = 0; lane < 64; ++lane) {
+            out[lane] = (int32_t)m16_dma_off(lane);
+            for (int j = 0; j < 4; ++j) out[64 + 64 * j + lane] = (int32_t)m16_lane_off(lane, 2) + m16_read_off(j, 2);
+            for (int T = 0; T < 2; ++T) out[320 + 64 * T + lane] = (int32_t)m16_lane_off(lane, 1) + m16_read_off(T, 1);
+            for (int e = 0; e < 8; ++e) out[448 + 8 * lane + e] = m16_feat(lane >> 4, e);
+            out[960 + lane] = 8 * m16_bias_oct(lane);
+        }
+    }
+    return N;
+}
+int dfn_debug_mfma16_layout(float* out, void* stream) {
+    if (!out) return fail(DFN_E_ARG, "dfn_debug_mfma16_layout: bad argument");
+    return launched(launch_mfma16_probe(out, (hipStream_t)stream), "mfma16_probe_kernel");
+}
 int dfn_debug_mfma_layout(float* out, void* stream) {
     if (!out) return fail(DFN_E_ARG, "dfn_debug_mfma_layout: bad argument");
     return launched(launch_mfma_probe(out, (hipStream_t)stream), "mfma_probe_kernel");

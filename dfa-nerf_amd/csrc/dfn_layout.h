@@ -76,6 +76,52 @@ DFN_HD int kslot_to_slot(int tier, int u, int h, int e) {
     return 32 * t + tile_feat(h, r);
 }
 
+// ---- 16x16x32: the f16 tier's MFMA shape on the same stream ----------------------------------------------------------------
+// The f16 tier (inference only) runs v_mfma_f32_16x16x32_f16: half the accumulator registers moved per multiply-accumulate of
+// the 32x32x16 shape.  C/D map: lane l, register j -> row 4 * (l >> 4) + j, column l & 15; A / B: lane l holds row / column
+// l & 15, k = 8 * (l >> 4) + e.  Lane l = (i = l & 15, k-group g = l >> 4).  A wave still owns 32 points: point group P0 = points
+// 0..15, P1 = points 16..31, two MFMAs per A operand.  Every 32-row tile of the stream is computed as two 16-row halves:
+//     T0 = rows with bit 3 clear, T1 = rows with bit 3 set: MFMA row i of half T = tile row m16_row(i, T).
+// After a layer, k-group g holds, per tile and point, rows 4 m .. 4 m + 3 for m = (0, 1, 4, 5)[g] (from T0) then m = (2, 3, 6, 7)[g]
+// (from T1): m16_feat(g, e).  Those eight rows, in that order, are exactly what k-slot (k-unit g >> 1 of the tile, half g & 1)
+// of the 32x32x16 map carries (kslot_to_slot): the A operand of (tile, T, K = 32 step v) is, per lane, ONE whole 16-byte slot of
+// the packed stream - slot (half g & 1, row m16_row(i, T)) of fragment 2 v + (g >> 1) of the tile - one ds_read_b128, and the
+// stream, its plan and its byte counts are those of the bf16 tier.
+// DFN_F16_LDS_PERM = 1: the LDS-DMA lanes of this tier swap bits 3 and 4 of the slot they fetch (m16_dma_off), which puts the 16
+// slots a k-group reads for one T next to each other in LDS: 256 contiguous bytes per 16 lanes, where the stream's own order gives
+// two runs of 128 bytes, 256 bytes apart.
+#ifndef DFN_F16_LDS_PERM
+#define DFN_F16_LDS_PERM 1
+#endif
+DFN_HD constexpr bool tier_m16(int tier) { return tier == TIER_F16; }
+DFN_HD constexpr int m16_row(int i, int T) { return (i & 7) + 16 * (i >> 3) + 8 * T; }
+// row (feature) within a 32-tile of element e of k-group g's operand / accumulator octet (e = 4 T + j)
+DFN_HD constexpr int m16_feat(int g, int e) { return (e & 3) + 8 * (e >> 2) + 4 * (g & 1) + 16 * (g >> 1); }
+// bytes from the slot of T0 to the slot of T1 in the LDS image of a fragment
+constexpr int M16_T_BYTES = DFN_F16_LDS_PERM ? 256 : 128;
+// byte offset inside a stream fragment that LDS-DMA lane `lane` fetches (it lands at LDS byte lane * 16 of the fragment's image)
+DFN_HD constexpr unsigned m16_dma_off(int lane) {
+    const unsigned x = (DFN_F16_LDS_PERM != 0) ? ((((unsigned)lane >> 3) ^ ((unsigned)lane >> 4)) & 1u) : 0u;
+    return ((unsigned)lane ^ (x * 0x18u)) * 16u;
+}
+// this lane's LDS byte offset, from the image of the first fragment of a quad (G = 2 tiles per k-unit: fragments [k-unit][tile]) or
+// pair (G = 1) of stream fragments, of its T0 slot of tile 0; tile 1: + FRAG_BYTES, T1: + M16_T_BYTES
+DFN_HD constexpr unsigned m16_lane_off(int lane, int G) {
+    const unsigned i = lane & 15, g = (unsigned)lane >> 4;
+    const unsigned slot = (DFN_F16_LDS_PERM != 0) ? i : (i & 7) + 16 * (i >> 3);
+    return (g >> 1) * (unsigned)(G * FRAG_BYTES) + (g & 1) * 512u + slot * 16u;
+}
+// Read `pos` (= fragment index within the 32-fragment slab: one read per stream fragment, in stream order) of a G-tile group: the
+// byte offset, from the slab's image + m16_lane_off(lane, G), of the slot the lane reads.  G = 2: reads 4 q .. 4 q + 3 are (tile 0, T0),
+// (tile 0, T1), (tile 1, T0), (tile 1, T1) of the K = 32 step whose fragments are 4 q .. 4 q + 3; G = 1: reads 2 q, 2 q + 1 are T0, T1 of
+// fragments 2 q, 2 q + 1.  Every k-unit count of the programs is even and the G = 1 groups close a pass, so no quad or pair
+// straddles a slab.
+DFN_HD constexpr int m16_read_off(int pos, int G) {
+    return (G == 2 ? (pos & ~3) + ((pos >> 1) & 1) : (pos & ~1)) * FRAG_BYTES + (pos & 1) * M16_T_BYTES;
+}
+// the lane's eight bias values of a tile (T0's four rows, then T1's) inside a bias vector ([tile][half][16] floats), in units of 8
+DFN_HD constexpr int m16_bias_oct(int lane) { return 2 * ((lane >> 4) & 1) + (lane >> 5); }
+
 // ---- architecture (scripts/test_obama.sh: hidden 256, z 256, dim_signal 96, deform on) -----------
 constexpr int HID = 256, ZDIM = 256, NPE = 60, NPEV = 24, NSIG = 96, NET = 42, DH = 64;
 

@@ -38,6 +38,7 @@ hipError_t launch_mfma_chain(bool f16, int lds2, int valu2, const void* frags, c
                              unsigned long long* clk, hipStream_t st);
 hipError_t launch_to8b(const float* x, long n, unsigned char* out, hipStream_t st);
 hipError_t launch_mfma_probe(float* out, hipStream_t st);
+hipError_t launch_mfma16_probe(float* out, hipStream_t st);
 hipError_t launch_adam_multi(const DfnAdamItem* items, const void* chunks, int n_chunks, float lr, double beta1, double beta2,
                              float eps, float bias_c1, float bias_c2_sqrt, hipStream_t st);
 }  // namespace dfn

@@ -756,6 +756,24 @@ hipError_t launch_mfma_probe(float* out, hipStream_t st) {
     hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, st, out);
     return hipGetLastError();
 }
+// The f16 tier's shape (dfn_layout.h "16x16x32"): A row / B column l & 15, k = 8 (l >> 4) + e; D row 4 (l >> 4) + j, column l & 15.
+// Full, asymmetric integer operands (exact in f16 and in the f32 sum): a transposed or group-swapped map shows in the product.
+__global__ void mfma16_probe_kernel(float* out) {
+    const int lane = threadIdx.x, i = lane & 15, g = lane >> 4;
+    f16x8 a, b;
+    for (int e = 0; e < 8; ++e) {
+        const int k = 8 * g + e;
+        a[e] = (_Float16)(float)((7 * i + 3 * k) % 13 + 1);
+        b[e] = (_Float16)(float)((5 * k + 11 * i) % 17 + 1);
+    }
+    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, d, 0, 0, 0);
+    for (int j = 0; j < 4; ++j) out[(4 * g + j) * 16 + i] = d[j];
+}
+hipError_t launch_mfma16_probe(float* out, hipStream_t st) {
+    hipLaunchKernelGGL(mfma16_probe_kernel, dim3(1), dim3(64), 0, st, out);
+    return hipGetLastError();
+}
 
 
 // ---- Adam over a list of tensors (run_nerf_com_trainExpLater.py:522-547: torch.optim.Adam, betas (0.9, 0.999)) -------

@@ -61,6 +61,13 @@ template <> struct TierCfg<TIER_F16X3> {
 constexpr int RING_SLOTS = 3;
 constexpr int RING_BYTES = RING_SLOTS * SLAB_BYTES;
 
+// ---- f16 tier: v_mfma_f32_16x16x32_f16 on the unchanged weight stream (lane maps: dfn_layout.h "16x16x32") ----------------------
+// byte offset inside a global fragment that LDS-DMA lane `lane` (LDS position lane * 16) fetches
+template <int TIER> DFN_DEV size_t dma_lane_off(int lane) {
+    if constexpr (tier_m16(TIER)) return m16_dma_off(lane);
+    else return (size_t)lane * 16;
+}
+
 // ---- a vector of NT 32-feature tiles held as MFMA B operand ------------------------------------------
 // local slot L (0..16*NT-1) of this lane = tile L>>4, accumulator register L&15.
 template <int TIER, int NT> struct Vec;
@@ -131,11 +138,11 @@ DFN_DEV void stream_issue_piece(const Stream& s, lds_char* ring, int wave, int l
         // wave-uniform base in an SGPR pair + 32-bit lane offset (the "saddr" form): no 64-bit VALU address arithmetic per
         // piece (interleaved A/B on one box, f16 C2: 35.10 -> 34.42 ms)
         const gchar_c* sb = (const gchar_c*)(s.pf_ptr + f * FRAG_BYTES);
-        const unsigned voff = (unsigned)lane * 16u;
+        const unsigned voff = (unsigned)dma_lane_off<TIER>(lane);
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb), "s"(dst) : "memory", "m0");
     } else {
         __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(s.pf_ptr + (size_t)lane * 16 + f * FRAG_BYTES),
+            (const __attribute__((address_space(1))) void*)(s.pf_ptr + (size_t)dma_lane_off<TIER>(lane) + f * FRAG_BYTES),
             (DFN_LDS void*)(ring + s.pf_slot * SLAB_BYTES + f * FRAG_BYTES), 16, 0, 0);
     }
 }
@@ -221,7 +228,13 @@ DFN_DEV void slab_advance(Stream& s, lds_char* ring, int wave, int lane) {
 #endif
     s.rd_slot = (s.rd_slot + 1 == RING_SLOTS) ? 0u : s.rd_slot + 1;
     s.rd_off = s.rd_slot * SLAB_BYTES;
-    s.rd_vaddr = (unsigned)(unsigned long)ring + (unsigned)lane * 16u + s.rd_off;
+    if constexpr (tier_m16(TIER)) {
+        // (computed from the lane id at every hand-over, behind an opaque copy: hoisted out of the pass loop the offset and its
+        // G = 1 form are two more registers that live through the whole kernel, which has none to spare)
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        s.rd_vaddr = (unsigned)(unsigned long)ring + m16_lane_off(l, 2) + s.rd_off;
+    } else s.rd_vaddr = (unsigned)(unsigned long)ring + (unsigned)lane * 16u + s.rd_off;
     s.pf_owed += C::LOADS_PER_SLAB;
 }
 
@@ -586,6 +599,26 @@ DFN_DEV void frag_read(u32x4& dst, unsigned vaddr, int pos) {      // pos = frag
     }
 }
 #undef DFN_FRAG_CASE
+// f16 tier: code = 2 * (fragment of the slab the lanes of k-groups 0, 1 read) + T
+#define DFN_FRAG_CASE(K)                                                                                      \
+    case 2 * (K):                                                                                             \
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(vaddr), "n"((K) * FRAG_BYTES) : "memory"); \
+        break;                                                                                                \
+    case 2 * (K) + 1:                                                                                         \
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(vaddr), "n"((K) * FRAG_BYTES + M16_T_BYTES) : "memory"); \
+        break;
+DFN_DEV void frag_read16(u32x4& dst, unsigned vaddr, int code) {
+    switch (code) {
+        DFN_FRAG_CASE(0) DFN_FRAG_CASE(1) DFN_FRAG_CASE(2) DFN_FRAG_CASE(3) DFN_FRAG_CASE(4) DFN_FRAG_CASE(5)
+        DFN_FRAG_CASE(6) DFN_FRAG_CASE(7) DFN_FRAG_CASE(8) DFN_FRAG_CASE(9) DFN_FRAG_CASE(10) DFN_FRAG_CASE(11)
+        DFN_FRAG_CASE(12) DFN_FRAG_CASE(13) DFN_FRAG_CASE(14) DFN_FRAG_CASE(15) DFN_FRAG_CASE(16) DFN_FRAG_CASE(17)
+        DFN_FRAG_CASE(18) DFN_FRAG_CASE(19) DFN_FRAG_CASE(20) DFN_FRAG_CASE(21) DFN_FRAG_CASE(22) DFN_FRAG_CASE(23)
+        DFN_FRAG_CASE(24) DFN_FRAG_CASE(25) DFN_FRAG_CASE(26) DFN_FRAG_CASE(27) DFN_FRAG_CASE(28) DFN_FRAG_CASE(29)
+        DFN_FRAG_CASE(30) DFN_FRAG_CASE(31)
+        default: __builtin_unreachable();
+    }
+}
+#undef DFN_FRAG_CASE
 // wait until at most `younger` LDS operations issued after the read of `r` are outstanding (they return in order); the
 // "+v" ties the wait to the register so that the MFMA consuming it cannot be scheduled above it
 DFN_DEV void frag_wait(u32x4& r, int younger) {
@@ -616,14 +649,30 @@ struct NoSide { DFN_DEV void operator()(int) const {} };      // work issued bet
 template <int TIER> struct Fetch {
     u32x4 buf[PF_DEPTH];
     template <class CT> DFN_DEV void load(int slot, int fp, Stream& s, const CT& c) { load(slot, fp, s, c, NoHook{}); }
-    template <class CT, class H> DFN_DEV void load(int slot, int fp, Stream& s, const CT& c, H&& hook) {
+    // gl (f16 tier only): tiles per k-unit of the group fragment fp belongs to.  Read fp of that tier is not fragment fp: reads
+    // 4 q .. 4 q + 3 of a G = 2 group are (tile 0, T0), (tile 0, T1), (tile 1, T0), (tile 1, T1) of the K = 32 step made of
+    // fragments 4 q .. 4 q + 3 ([k-unit][tile]: k-groups 0, 1 read k-unit 2 v, k-groups 2, 3 k-unit 2 v + 1); reads 2 q, 2 q + 1 of a
+    // G = 1 group are T0, T1 of fragments 2 q, 2 q + 1.  One read per fragment, in stream order: slab hand-over, ring and the
+    // spreading of the LDS-DMA pieces are those of the other tiers.
+    template <class CT, class H> DFN_DEV void load(int slot, int fp, Stream& s, const CT& c, H&& hook, int gl = 2) {
         using C = TierCfg<TIER>;
         constexpr int GAP = SLAB_FRAGS / C::LOADS_PER_SLAB;       // fragment reads between two DMA pieces
         if (fp % SLAB_FRAGS == 0) {
             slab_advance<TIER>(s, c.ring, c.wave, c.lane);
             hook();
         }
-        if constexpr (use_asm_fetch<TIER, CT>()) frag_read(buf[slot], s.rd_vaddr, fp % SLAB_FRAGS);
+        if constexpr (tier_m16(TIER)) {
+            const int off = m16_read_off(fp % SLAB_FRAGS, gl);
+            // (G = 1: the k-groups 2, 3 sit one fragment behind 0, 1, not two)
+            unsigned vaddr = s.rd_vaddr;
+            if (gl != 2) {
+                unsigned l = (unsigned)c.lane;
+                asm volatile("" : "+v"(l));
+                vaddr -= (l >> 5) << 10;
+            }
+            if constexpr (use_asm_fetch<TIER, CT>()) frag_read16(buf[slot], vaddr, 2 * (off / FRAG_BYTES) + (off % FRAG_BYTES != 0));
+            else buf[slot] = *(const lds_u32x4*)(c.ring + m16_lane_off(c.lane, gl) + s.rd_off + off);
+        } else if constexpr (use_asm_fetch<TIER, CT>()) frag_read(buf[slot], s.rd_vaddr, fp % SLAB_FRAGS);
         else buf[slot] = *(const lds_u32x4*)(c.ring + c.lane * 16 + s.rd_off + (fp % SLAB_FRAGS) * FRAG_BYTES);
 #ifdef DFN_EXP_DBLLDS       // experiment: what does the LDS fragment traffic cost?  read every fragment a second time
         {                   // (same results, +100 % fragment reads; the neighbouring fragment so that the data differ)
@@ -652,10 +701,61 @@ template <int TIER> struct Fetch {
 // TAIL: number of fragments that follow this group in the pass (-1 = plenty): no prefetch past the end.
 // f16x3 tier: fragments [ku][g][hi, lo'], three MFMAs per (ku, g): acc += hi.hi, accx += hi.lo' + lo'.hi; accx (the terms
 // scaled by 2^11) is folded into acc at the end of the group - every caller reads acc only after gemm_group returns.
-template <int TIER, int G, int KU, int NTB, int TAIL = -1, class CT, class H = NoHook, class SD = NoSide>
+// f16 tier (16x16x32 MFMAs, above): acc[g] holds tile g as [point group P][T][4 rows] = register 8 P + 4 T + j, b.u[2 v + P] is the
+// K = 32 step v of point group P; per step and tile, reads (T0, T1) and four MFMAs.  GN: tiles per k-unit of the group that FOLLOWS
+// in the pass (the fragment ring reads PF_DEPTH ahead, across the end of the group: only the last G = 2 group of a pass differs).
+template <int TIER, int G, int KU, int NTB, int TAIL = -1, int GN = G, class CT, class H = NoHook, class SD = NoSide>
 DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch<TIER>& fe, Stream& s,
                         const CT& c, H&& hook = H{}, SD&& side = SD{}) {
-    if constexpr (TIER == TIER_F16X3) {
+    if constexpr (tier_m16(TIER)) {
+        static_assert(KU % 2 == 0 && (G == 1 || G == 2) && PF_DEPTH == 4, "K = 32 steps are fragment pairs; the ring holds one quad");
+        // the recorder (store_tiles_T, rec_vals, rec_mask_pair*) reads c.half and the operand vectors in the 32x32x16 layout
+        static_assert(!CT::rec_on, "the f16 tier is inference only: no recorder for the 16x16x32 layout");
+        // a one-tile group may only be followed by one-tile groups (they close a pass): GN of every group is at most its G
+        static_assert(GN <= G, "a two-tile group behind a one-tile group: the ring would have read its first fragments as a pair");
+        constexpr bool ASM = use_asm_fetch<TIER, CT>();
+#pragma unroll
+        for (int v = 0; v < KU / 2; ++v) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+#pragma unroll
+                for (int T = 0; T < 2; ++T) {
+                    const int left = (KU / 2 - v) * 2 * G - 2 * g - T - 1;      // reads after this one in the group
+                    if constexpr (ASM) {
+                        const int after = (TAIL < 0) ? PF_DEPTH : left + TAIL;             // ... in the pass
+                        frag_wait(fe.buf[f % PF_DEPTH], after < PF_DEPTH - 1 ? after : PF_DEPTH - 1);
+                    }
+                    const f16x8 a = __builtin_bit_cast(f16x8, fe.buf[f % PF_DEPTH]);
+                    if constexpr (!ASM) {
+                        if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook, left >= PF_DEPTH ? G : GN);
+                    }
+#pragma unroll
+                    for (int P = 0; P < 2; ++P) {
+                        const int o = 8 * P + 4 * T;
+                        f32x4 d = {acc[g][o], acc[g][o + 1], acc[g][o + 2], acc[g][o + 3]};
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b.u[2 * v + P], d, 0, 0, 0);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[g][o + j] = d[j];
+                    }
+                    if constexpr (ASM) {
+                        if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook, left >= PF_DEPTH ? G : GN);
+                    }
+#ifdef DFN_GEMM_SCHEDBAR
+                    if constexpr (!ASM) __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
+#endif
+                    ++f;
+                }
+                if (G == 2) side(2 * v + g);      // (one call per stream k-unit, as in the other tiers)
+            }
+            if (G == 1) {
+                side(2 * v);
+                side(2 * v + 1);
+            }
+#ifdef DFN_PIPE_SCHEDBAR
+            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
+#endif
+        }
+    } else if constexpr (TIER == TIER_F16X3) {
         // (the register ring is PF_DEPTH fragments = two (hi, lo') pairs ahead; a depth of 8 parks 6-14 more VGPRs in AGPRs)
         constexpr int D = PF_DEPTH;
         f32x16 accx[G];
@@ -753,7 +853,9 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
 DFN_DEV float relu_(float x) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
 
 // bias vectors live in LDS as [tile][half][16]
-template <int G>
+// M16 (f16 tier): `half` is the lane's m16_bias_oct; its 8 floats (T0's rows, T1's rows) start both point groups: written as four
+// reads like the other tiers (the pipelined layers issue them one by one), of which two repeat an address - the compiler merges them
+template <int G, bool M16 = false>
 DFN_DEV void acc_init(f32x16 (&acc)[G], const lds_f32* bias_lds, int half) {
 #ifdef DFN_EXP_NOINIT     // timing experiment (wrong results): accumulators start at zero, no bias reads from LDS
 #pragma unroll
@@ -764,24 +866,24 @@ DFN_DEV void acc_init(f32x16 (&acc)[G], const lds_f32* bias_lds, int half) {
 #endif
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const lds_f32x4* p = (const lds_f32x4*)(bias_lds + g * 32 + half * 16);
+        const lds_f32x4* p = (const lds_f32x4*)(bias_lds + g * 32 + half * (M16 ? 8 : 16));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x4 v = p[q];
+            const f32x4 v = p[M16 ? (q & 1) : q];
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[g][4 * q + e] = v[e];
         }
     }
 }
 // acc = relu(acc) + bias   (where a constant joins after the ReLU: decoder.py:316-321, 118-119)
-template <int G>
+template <int G, bool M16 = false>
 DFN_DEV void acc_relu_add(f32x16 (&acc)[G], const lds_f32* bias_lds, int half) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const lds_f32x4* p = (const lds_f32x4*)(bias_lds + g * 32 + half * 16);
+        const lds_f32x4* p = (const lds_f32x4*)(bias_lds + g * 32 + half * (M16 ? 8 : 16));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x4 v = p[q];
+            const f32x4 v = p[M16 ? (q & 1) : q];
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[g][4 * q + e] = relu_(acc[g][4 * q + e]) + v[e];
         }
@@ -943,9 +1045,10 @@ DFN_DEV void epi_word(const f32x16 (&acc)[2], Vec<TIER, NT>& v, int t0, int w) {
     v.u[2 * (t0 + g) + h] = __builtin_bit_cast(pk8, q);
 }
 // bias read q (0..7) of a tile pair's accumulator initialisation (one ds_read_b128 = 4 registers): acc_init, piecewise
+template <bool M16 = false>
 DFN_DEV void init_quad(f32x16 (&acc)[2], const lds_f32* bias_lds, int half, int q) {
     const int g = q >> 2, qq = q & 3;
-    const f32x4 v = ((const lds_f32x4*)(bias_lds + g * 32 + half * 16))[qq];
+    const f32x4 v = ((const lds_f32x4*)(bias_lds + g * 32 + half * (M16 ? 8 : 16)))[M16 ? (qq & 1) : qq];
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[g][4 * qq + e] = v[e];
 }
@@ -968,7 +1071,7 @@ template <int TIER, int OT, int KU, bool RELU> struct PipeSide {
         if (bias_next && ku >= ES) {
 #pragma unroll
             for (int q = 0; q < QPS; ++q)
-                if ((ku - ES) * QPS + q < 8) init_quad(other, bias_next, half, (ku - ES) * QPS + q);
+                if ((ku - ES) * QPS + q < 8) init_quad<tier_m16(TIER)>(other, bias_next, half, (ku - ES) * QPS + q);
         }
     }
 };
@@ -977,14 +1080,14 @@ DFN_DEV void layer_pipe(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_
                         Stream& s, const CT& c) {
     static_assert(OT % 2 == 0 && KU >= 2, "tile pairs");
     f32x16 acc[2][2];
-    acc_init<2>(acc[0], bias, c.half);
+    acc_init<2, tier_m16(TIER)>(acc[0], bias, c.half);
 #pragma unroll
     for (int tg = 0; tg < OT / 2; ++tg) {
         const int cur = tg & 1;
         const PipeSide<TIER, OT, KU, RELU> side = {acc[cur ^ 1], out, tg + 1 < OT / 2 ? bias + (tg + 1) * 64 : nullptr,
                                                    tg > 0 ? 2 * (tg - 1) : -1, c.half};
         gemm_group<TIER, 2, KU, NTB>(acc[cur], in, f, fe, s, c, NoHook{}, side);
-        if (KU - PipeSide<TIER, OT, KU, RELU>::ES < 1 && tg + 1 < OT / 2) acc_init<2>(acc[cur ^ 1], bias + (tg + 1) * 64, c.half);
+        if (KU - PipeSide<TIER, OT, KU, RELU>::ES < 1 && tg + 1 < OT / 2) acc_init<2, tier_m16(TIER)>(acc[cur ^ 1], bias + (tg + 1) * 64, c.half);
     }
     acc_to_vec<TIER, 2, OT, RELU>(acc[(OT / 2 - 1) & 1], out, OT - 2);        // the last pair: not overlapped
 }
@@ -1065,7 +1168,7 @@ DFN_DEV void layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_f32* 
 #pragma unroll
         for (int tg = 0; tg < OT / 2; ++tg) {
             f32x16 acc[2];
-            acc_init<2>(acc, bias + tg * 64, c.half);
+            acc_init<2, tier_m16(TIER)>(acc, bias + tg * 64, c.half);
             bits = 0;
             gemm_group<TIER, 2, KU, NTB>(acc, in, f, fe, s, c, NoHook{},
                                          RecSide32<OT, KU, CT>{c, out, rec_row, (rec_mask < 0 || tg == 0) ? -1 : rec_mask + tg - 1, tg - 1, bits});
@@ -1080,7 +1183,7 @@ DFN_DEV void layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_f32* 
 #pragma unroll
     for (int tg = 0; tg < OT / 2; ++tg) {
         f32x16 acc[2];
-        acc_init<2>(acc, bias + tg * 64, c.half);
+        acc_init<2, tier_m16(TIER)>(acc, bias + tg * 64, c.half);
         if constexpr (SPREAD) {
             gemm_group<TIER, 2, KU, NTB>(acc, in, f, fe, s, c, NoHook{}, RecSide<TIER, OT, KU, CT, RELU>{c, out, rec_row, tg - 1, {}});
         } else {
@@ -1107,14 +1210,14 @@ DFN_DEV void layer_skip(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_
 #pragma unroll
     for (int tg = 0; tg < OT / 2; ++tg) {
         f32x16 acc[2];
-        acc_init<2>(acc, bias + tg * 64, c.half);
+        acc_init<2, tier_m16(TIER)>(acc, bias + tg * 64, c.half);
         auto flush = [&] {
             if (pend) rec_vals<TIER>(c, rec_row + 64 * (tg - 1), out, 2 * (tg - 1));
             pend = false;
         };
         gemm_group<TIER, 2, KU, NTB>(acc, in, f, fe, s, c, flush);
         rec_mask_pair(c, mask_dword0 < 0 ? -1 : mask_dword0 + tg, acc);                 // ReLU bits of the pre-skip value
-        acc_relu_add<2>(acc, bias2 + tg * 64, c.half);
+        acc_relu_add<2, tier_m16(TIER)>(acc, bias2 + tg * 64, c.half);
         gemm_group<TIER, 2, KU2, NTB2>(acc, in2, f, fe, s, c, flush);
         flush();
         acc_to_vec<TIER, 2, OT, false>(acc, out, 2 * tg);                               // post-skip value (no ReLU)
@@ -1169,6 +1272,66 @@ DFN_DEV void posenc(Vec<TIER, NT>& v, const float (&p)[3], int half) {
         }
         const bool ok = half ? ok1 : ok0;
         v.set(L, ok ? val : 0.f);
+    }
+}
+
+// f16 tier (16x16x32 MFMAs): lane (i = lane & 15, k-group g = lane >> 4) holds, of tile t and point group P, in local slot
+// 16 t + 8 P + e the column 32 t + 8 (e >> 2) + (e & 3) + 4 (g & 1) + 16 (g >> 1) - where a GEMM of that tier leaves output feature
+// `column` (gemm_group), so the torso's `deform(p) + p` stays a lane-local add.  The same values as posenc<TIER_F16> (hardware sin
+// on revolutions), the same number of them per lane; p0 / p1: the lane's points of P0 / P1.
+template <int NT, int NCOL>
+DFN_DEV void posenc16(Vec<TIER_F16, NT>& v, const float (&p0)[3], const float (&p1)[3], int lane) {
+    const bool g0 = (lane & 16) != 0, g1 = (lane & 32) != 0;
+    const float ph[2][3] = {{p0[0] * 0.5f, p0[1] * 0.5f, p0[2] * 0.5f}, {p1[0] * 0.5f, p1[1] * 0.5f, p1[2] * 0.5f}};
+#pragma unroll
+    for (int L = 0; L < 16 * NT; ++L) {
+        const int P = (L >> 3) & 1, e = L & 7;
+        const int base = 32 * (L >> 4) + 8 * (e >> 2) + (e & 3);            // compile-time
+        float r[4], q[4];
+        bool ok[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                                       // k-group k
+            const int col = base + 4 * (k & 1) + 16 * (k >> 1);
+            ok[k] = col < NCOL;
+            const int o = ok[k] ? col / 6 : 0, a = ok[k] ? (col % 6) % 3 : 0;
+            r[k] = ph[P][a] * ((float)(1 << o) * 0.5f);
+            q[k] = (ok[k] && (col % 6) >= 3) ? 0.25f : 0.f;
+        }
+        if (!ok[0] && !ok[1] && !ok[2] && !ok[3]) {
+            v.set(L, 0.f);
+            continue;
+        }
+        const float rr = g1 ? (g0 ? r[3] : r[2]) : (g0 ? r[1] : r[0]);
+        const float qq = g1 ? (g0 ? q[3] : q[2]) : (g0 ? q[1] : q[0]);
+        const bool okk = g1 ? (g0 ? ok[3] : ok[2]) : (g0 ? ok[1] : ok[0]);
+        const float val = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(rr) + qq);
+        v.set(L, okk ? val : 0.f);
+    }
+}
+// The interface of the MLP passes is the other tiers': a lane brings the point lane & 31 and takes its outputs in lanes 0..31.
+// Inside, the lane works on points lane & 15 (P0) and 16 + (lane & 15) (P1): one is its own, the other lane ^ 16's.
+DFN_DEV void m16_pair(const float (&x)[3], int lane, float (&x0)[3], float (&x1)[3]) {
+    const bool up = (lane & 16) != 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float o = __shfl_xor(x[k], 16);
+        x0[k] = up ? o : x[k];
+        x1[k] = up ? x[k] : o;
+    }
+}
+// output row j < 4 of a one-tile group: k-group 0 holds it, P0 in register j, P1 in register 8 + j -> lanes 0..31 by point
+DFN_DEV float m16_out(const f32x16& acc, int j, int lane) {
+    const float o = __shfl_xor(acc[8 + j], 16);
+    return (lane & 16) ? o : acc[j];
+}
+template <int TIER, int NT, int NCOL>
+DFN_DEV void posenc_of(Vec<TIER, NT>& v, const float (&p)[3], int half, int lane) {
+    if constexpr (tier_m16(TIER)) {
+        float p0[3], p1[3];
+        m16_pair(p, lane, p0, p1);
+        posenc16<NT, NCOL>(v, p0, p1, lane);
+    } else {
+        posenc<TIER, NT, NCOL>(v, p, half);
     }
 }
 
@@ -1315,7 +1478,7 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
         Vec<TIER, 1> vview;
         float dhat[3];
         dref.load(dhat);
-        posenc<TIER, 1, NPEV>(vview, dhat, c.half);
+        posenc_of<TIER, 1, NPEV>(vview, dhat, c.half, c.lane);
         rec_vec<TIER, 1>(c, r_trunk + RecMap::T_VIEW, vview);
         bool pend = false;      // recorder values of pair tg - 1, issued at the next slab hand-over (NoHook)
         int ptg = 0;
@@ -1326,9 +1489,17 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
 #pragma unroll
         for (int tg = 0; tg < HT / 2; ++tg) {
             f32x16 acc[2];
-            acc_init<2>(acc, bias + b_view + tg * 64, c.half);
+            acc_init<2, tier_m16(TIER)>(acc, bias + b_view + tg * 64, c.half);
             gemm_group<TIER, 2, P::KU_ACT, HT>(acc, a7, f, fe, s, c, flush);
-            gemm_group<TIER, 2, P::KU_VIEW, 1>(acc, vview, f, fe, s, c, flush);
+            // (f16 tier: the reads ahead of the last pair's view group are the sigma tile's, a one-tile group.  This is the ONE place
+            // of a pass where a two-tile group is followed by a one-tile group: a new one needs GN = 1 as well - the host walk of
+            // tests/test_mfma16_host.py and the f32-tier comparison of tests/test_gpu_mfma16.py fail on a wrong slot)
+            if constexpr (tier_m16(TIER)) {
+                if (tg == HT / 2 - 1) gemm_group<TIER, 2, P::KU_VIEW, 1, -1, 1>(acc, vview, f, fe, s, c, flush);
+                else gemm_group<TIER, 2, P::KU_VIEW, 1>(acc, vview, f, fe, s, c, flush);
+            } else {
+                gemm_group<TIER, 2, P::KU_VIEW, 1>(acc, vview, f, fe, s, c, flush);
+            }
             flush();
             acc_to_vec<TIER, 2, HT, true>(acc, hid, 2 * tg);
             if constexpr (tier_is16(TIER)) rec_mask_pair_packed<TIER, HT>(c, m_trunk + RecMap::TM_H + tg, hid, 2 * tg);
@@ -1337,20 +1508,27 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
             ptg = tg;
         }
         f32x16 acc1[1];
-        acc_init<1>(acc1, bias + b_view + 256, c.half);
+        acc_init<1, tier_m16(TIER)>(acc1, bias + b_view + 256, c.half);
         gemm_group<TIER, 1, P::KU_ACT, HT>(acc1, a7, f, fe, s, c, flush);
         gemm_group<TIER, 1, P::KU_VIEW, 1>(acc1, vview, f, fe, s, c, flush);
         flush();
-        o.sigma = acc1[0][0];
+        if constexpr (tier_m16(TIER)) o.sigma = m16_out(acc1[0], 0, c.lane);
+        else o.sigma = acc1[0][0];
     }
     // feat_out + sigmoid   (decoder.py:344-347)
     {
         f32x16 acc1[1];
-        acc_init<1>(acc1, bias + b_out, c.half);
+        acc_init<1, tier_m16(TIER)>(acc1, bias + b_out, c.half);
         gemm_group<TIER, 1, P::KU_ACT, HT, 0>(acc1, hid, f, fe, s, c);    // last op of the pass
-        o.r = sigmoidf_(acc1[0][0]);
-        o.g = sigmoidf_(acc1[0][1]);
-        o.b = sigmoidf_(acc1[0][2]);
+        if constexpr (tier_m16(TIER)) {
+            o.r = sigmoidf_(m16_out(acc1[0], 0, c.lane));
+            o.g = sigmoidf_(m16_out(acc1[0], 1, c.lane));
+            o.b = sigmoidf_(m16_out(acc1[0], 2, c.lane));
+        } else {
+            o.r = sigmoidf_(acc1[0][0]);
+            o.g = sigmoidf_(acc1[0][1]);
+            o.b = sigmoidf_(acc1[0][2]);
+        }
     }
     return o;
 }
@@ -1361,7 +1539,7 @@ DFN_DEV MlpOut mlp_head(const float (&p)[3], const DhatRef& dhat, const lds_f32*
                         const CT& c) {
     using P = Prog<TIER, HT>;
     Vec<TIER, 2> pe;
-    posenc<TIER, 2, NPE>(pe, p, c.half);
+    posenc_of<TIER, 2, NPE>(pe, p, c.half, c.lane);
     rec_vec<TIER, 2>(c, RecMap::H_PE, pe);
     Vec<TIER, HT> act;
     int f = 0;
@@ -1379,7 +1557,7 @@ DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32
                          const CT& c) {
     using P = Prog<TIER, HT>;
     Vec<TIER, 2> pe;
-    posenc<TIER, 2, NPE>(pe, p, c.half);
+    posenc_of<TIER, 2, NPE>(pe, p, c.half, c.lane);
     rec_vec<TIER, 2>(c, RecMap::S_PE, pe);
     Vec<TIER, 2> ve, vs, vn;
     int f = 0;
@@ -1399,10 +1577,10 @@ DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32
     ve = vn;
     {   // signal net: its skip input is the per-frame pose signal -> a constant added after the ReLU
         f32x16 acc[2];
-        acc_init<2>(acc, bias + P::T_B_S3, c.half);
+        acc_init<2, tier_m16(TIER)>(acc, bias + P::T_B_S3, c.half);
         gemm_group<TIER, 2, P::KU_D, 2>(acc, vs, f, fe, s, c);
         rec_mask_pair(c, RecMap::S_MD0 + 7, acc);
-        acc_relu_add<2>(acc, bias + P::T_B_SSKIP, c.half);
+        acc_relu_add<2, tier_m16(TIER)>(acc, bias + P::T_B_SSKIP, c.half);
         acc_to_vec<TIER, 2, 2, false>(acc, vn, 0);
         rec_vals<TIER>(c, RecMap::S_D0 + 64 * 7, vn, 0);
         vs = vn;
@@ -1415,13 +1593,13 @@ DFN_DEV MlpOut mlp_torso(const float (&p)[3], const DhatRef& dhat, const lds_f32
     Vec<TIER, 4> pd;      // tiles 0,1: deformed PE (60 valid); tiles 2,3: deformed pose signal (42 valid)
     {
         f32x16 acc[2];
-        acc_init<2>(acc, bias + P::T_B_EO, c.half);
+        acc_init<2, tier_m16(TIER)>(acc, bias + P::T_B_EO, c.half);
         gemm_group<TIER, 2, P::KU_D, 2>(acc, ve, f, fe, s, c);
 #pragma unroll
         // (f16x3: pe.get is hi + 2^-11 lo', the f32 encoding to ~2^-22 relative - not the exact value the f32 tier adds;
         // tests/test_f16x3_host.py models it)
         for (int L = 0; L < 32; ++L) pd.set(L, acc[L >> 4][L & 15] + pe.get(L));
-        acc_init<2>(acc, bias + P::T_B_SO, c.half);
+        acc_init<2, tier_m16(TIER)>(acc, bias + P::T_B_SO, c.half);
         gemm_group<TIER, 2, P::KU_D, 2>(acc, vs, f, fe, s, c);
 #pragma unroll
         for (int L = 0; L < 32; ++L) pd.set(32 + L, acc[L >> 4][L & 15]);

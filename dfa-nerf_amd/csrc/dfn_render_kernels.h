@@ -197,7 +197,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
 #define DFN_PIPE_TWO_HEAD 1
 #endif
     typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, (DFN_PIPE != 0) && TRAIN == 0 && (!TWO || DFN_PIPE_TWO != 0), TRAIN != 0 && ACT4> CtxK;      // (fused step: act_T in MX-fp4 unless ACT4 is off)
-    CtxK ctx = {lds, wave, lane, lane >> 5, {}};
+    CtxK ctx = {lds, wave, lane, tier_m16(TIER) ? m16_bias_oct(lane) : lane >> 5, {}};      // (f16: dfn_mlp.h acc_init)
     typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, (DFN_PIPE != 0) && TRAIN == 0 && (!TWO || DFN_PIPE_TWO != 0 || DFN_PIPE_TWO_HEAD != 0), TRAIN != 0 && ACT4> CtxH;   // the head's passes
     constexpr bool two = TWO;
     const int NF = TRAIN == 1 ? 0 : F.n_fine;     // TRAIN == 1: the training forward is the reference's coarse renderer
@@ -803,7 +803,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     // (128-wide program: the asm fragment fetch, as in the render kernels - with the compiler's own reads the 16-bit torso kernel
     // spills 96 VGPRs to scratch, which the build refuses; tools/check_inflight.py runs on these kernels too)
     typedef CtxT<REC, HT != 8, REC> CtxD;
-    CtxD ctx = {lds, wave, lane, lane >> 5, {}};
+    CtxD ctx = {lds, wave, lane, tier_m16(TIER) ? m16_bias_oct(lane) : lane >> 5, {}};
     ctx.rec.act_T = nullptr;
     ctx.rec.masks = nullptr;
 

@@ -572,6 +572,13 @@ def to8b(x):
     return out
 
 
+def mfma16_layout_probe(device="cuda"):
+    """A x B of dfn_debug_mfma16_layout (include/dfanerf.h): [16, 16]"""
+    out = torch.zeros(16, 16, dtype=torch.float32, device=device)
+    check(lib.dfn_debug_mfma16_layout(_ptr(out), _stream()), "dfn_debug_mfma16_layout")
+    return out
+
+
 def mfma_layout_probe(device="cuda"):
     out = torch.zeros(3, 32, 32, dtype=torch.float32, device=device)
     check(lib.dfn_debug_mfma_layout(_ptr(out), _stream()), "dfn_debug_mfma_layout")

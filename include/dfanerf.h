@@ -504,6 +504,18 @@ int dfn_to8b(const float* x, long n, uint8_t* out, void* stream);
  * A = (row,k) / B = (k,col) probes and writes D as the kernels interpret it: out[3][32][32] (bf16, f32, f16).
  * Used by tests to pin the fragment maps. */
 int dfn_debug_mfma_layout(float* out, void* stream);
+/* The f16 tier's v_mfma_f32_16x16x32_f16 (csrc/dfn_layout.h "16x16x32").
+ * dfn_mfma16_map: host only.  The lane maps the f16 kernels are compiled with, as int32 (returns the count, 1024; out may be NULL):
+ *   [0, 64)      dma[lane]        byte offset inside a stream fragment that LDS-DMA lane `lane` fetches to LDS byte lane * 16
+ *   [64, 320)    rd2[j][lane]     LDS byte offset, from the image of the first of the four fragments [k-unit 2 v, 2 v + 1][tile 0, 1]
+ *                                 of a K = 32 step, of the 16 bytes the lane reads as A operand j = 2 * tile + T
+ *   [320, 448)   rd1[T][lane]     the same for a one-tile group, from the image of fragment 2 v of the pair
+ *   [448, 960)   feat[lane][e]    row within a 32-tile of element e of the lane's operand / accumulator octet
+ *   [960, 1024)  bias[lane]       float offset of the lane's octet inside the [tile][half][16] bias vectors
+ * dfn_debug_mfma16_layout: one v_mfma_f32_16x16x32_f16 on A[i][k] = (7 i + 3 k) % 13 + 1, B[k][c] = (5 k + 11 c) % 17 + 1, filled and
+ * written out through the maps the kernels assume: out[16][16] = A x B. */
+long dfn_mfma16_map(int32_t* out, long capacity);
+int dfn_debug_mfma16_layout(float* out, void* stream);
 /* Power-ceiling probe (bench.py `roofline.power_ceiling`): the renderer's inner loop reduced to its cost drivers - 8 waves per
  * workgroup, one workgroup per compute unit, the tier's v_mfma_f32_32x32x16 on two alternating accumulator sets with
  * `lds_reads_per_2` 1-KiB fragment reads from LDS and `valu_per_2` convert / max instructions per TWO MFMAs - on the caller's
