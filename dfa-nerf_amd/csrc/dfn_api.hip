@@ -244,6 +244,14 @@ int counts_ok(int n_coarse, int n_fine, const char* who) {
         return fail(DFN_E_ARG, std::string(who) + ": the hierarchical mode (n_fine > 0) needs n_coarse = 32 or 64");
     return DFN_OK;
 }
+// the sample counts of a z launch (dfn_render_z_fwd[_u8]): the depths come from memory, there is no fine pass, and the kernel's LDS
+// holds 192 of them per ray
+int z_counts_ok(int n_coarse, int n_fine, const char* who) {
+    if (n_fine != 0 || n_coarse < 32 || n_coarse > 192 || n_coarse % 32)
+        return fail(DFN_E_ARG, std::string(who) + ": caller-supplied depths need n_fine == 0 and n_coarse (the depths per ray) a multiple of 32 "
+                                                  "in 32 ... 192");
+    return DFN_OK;
+}
 int smo_ok(int smo_size, const char* who) {
     if (smo_size < 0 || smo_size > 8 || (smo_size & 1)) return fail(DFN_E_ARG, std::string(who) + ": smo_size must be 0, 2, 4, 6 or 8");
     return DFN_OK;
@@ -393,13 +401,23 @@ struct AuxOut {
 struct RaysIn {
     const float *rays, *bounds;
 };
+// the per-ray depths of a z launch (dfn_render_z_fwd[_u8]): f32 [ray_count, n_coarse]
+struct ZIn {
+    const float* zvals;
+};
 static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                            const float* bias_head, const float* bias_torso, const float* bg_f32,
                            const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
                            float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream,
-                           const AuxOut* aux = nullptr, const RaysIn* rin = nullptr) {
+                           const AuxOut* aux = nullptr, const RaysIn* rin = nullptr, const ZIn* zin = nullptr) {
     int width;
-    if (take_width(tier, width, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
+    const std::string who = zin ? "dfn_render_z_fwd" : "dfn_render_fwd";      // the name the shared checks report under
+    if (take_width(tier, width, who.c_str()) != DFN_OK) return DFN_E_ARG;
+    // caller-supplied depths: the kernels exist in the inference tiers only, without an aux and without a rays form
+    if (zin && (tier == DFN_TIER_BF16 || aux || rin))
+        return fail(DFN_E_ARG, "dfn_render_z_fwd: caller-supplied depths exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
+                               "(bf16 is the training tier)");
+    if (zin && !zin->zvals) return fail(DFN_E_ARG, "dfn_render_z_fwd: zvals is NULL (dfn_render_fwd renders the frame's own linspace depths)");
     // caller-supplied rays: the kernels exist in the inference tiers only, and without an aux form
     if (rin && (tier == DFN_TIER_BF16 || aux))
         return fail(DFN_E_ARG, "dfn_render_rays_fwd: caller-supplied rays exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
@@ -410,19 +428,22 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
         return fail(DFN_E_ARG, "dfn_render_fwd_aux: opacity / depth outputs exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
                                "(bf16 is the training tier)");
     if (!tier_ok(tier) || !frame || !packed_head || !bias_head || !rgb_head)
-        return fail(DFN_E_ARG, "dfn_render_fwd: bad argument");
+        return fail(DFN_E_ARG, who + ": bad argument");
     const DfnFrame& F = *frame;
-    if (counts_ok(F.n_coarse, F.n_fine, "dfn_render_fwd") != DFN_OK) return DFN_E_ARG;
-    if (F.fields != 1 && F.fields != 2) return fail(DFN_E_ARG, "dfn_render_fwd: fields must be 1 or 2");
+    if ((zin ? z_counts_ok(F.n_coarse, F.n_fine, "dfn_render_z_fwd") : counts_ok(F.n_coarse, F.n_fine, "dfn_render_fwd")) != DFN_OK)
+        return DFN_E_ARG;
+    if (F.fields != 1 && F.fields != 2) return fail(DFN_E_ARG, who + ": fields must be 1 or 2");
     if (F.fields == 2 && (!packed_torso || !bias_torso || !rgb_com))
-        return fail(DFN_E_ARG, "dfn_render_fwd: torso inputs / rgb_com missing for fields == 2");
-    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, "dfn_render_fwd: no background given");
+        return fail(DFN_E_ARG, who + ": torso inputs / rgb_com missing for fields == 2");
+    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, who + ": no background given");
     if (F.ray_count <= 0) return DFN_OK;
+    // (the z kernels address their per-sample arrays by 32-bit byte offsets)
+    if (zin && (long)F.ray_count * F.n_coarse >= (1L << 30)) return fail(DFN_E_ARG, "dfn_render_z_fwd: too many rays per call (ray_count * n_coarse must stay under 2^30)");
     // (supplied rays: H, W, ray_begin, the intrinsics and the poses are ignored)
     if (!rin && (F.H <= 0 || F.W <= 0 || (!pix_index && (F.ray_begin < 0 || F.ray_begin + F.ray_count > F.H * F.W))))
-        return fail(DFN_E_ARG, "dfn_render_fwd: ray range outside the image");
+        return fail(DFN_E_ARG, who + ": ray range outside the image");
     RenderArgs A{};
-    const int rc = render_args(A, "dfn_render_fwd", tier, width, F, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8,
+    const int rc = render_args(A, who, tier, width, F, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8,
                                pix_index, rgb_head, rgb_com);
     if (rc != DFN_OK) return rc;
     A.w_head = weights_head;
@@ -441,6 +462,7 @@ static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_h
         A.rays = rin->rays;
         A.bounds = rin->bounds;
     }
+    if (zin) A.zvals = zin->zvals;      // (an inference launch records no ranks: that argument slot carries the depths, dfn_params.h)
     A.clock_probe = g_clock_probe;
     return launched(launch_render(tier, A, (hipStream_t)stream, width), "render_kernel");
 }
@@ -501,6 +523,33 @@ int dfn_render_rays_fwd_u8(int tier, const DfnFrame* frame, const void* packed_h
     const RaysIn rin = {rays, bounds};
     return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr,
                            (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, nullptr, &rin);
+}
+
+int dfn_render_z_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                     const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                     const int32_t* pix_index, float* rgb_head, float* rgb_com, float* weights_head, float* weights_com,
+                     float* z_vals, const float* zvals, void* stream) {
+    const ZIn zin = {zvals};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
+                           rgb_com, weights_head, weights_com, z_vals, 0, stream, nullptr, nullptr, &zin);
+}
+
+int dfn_render_z_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                        const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                        const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, const float* zvals, void* stream) {
+    const ZIn zin = {zvals};
+    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
+                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, nullptr, nullptr, &zin);
+}
+
+int dfn_fine_depths(const DfnFrame* frame, const float* weights, float* z_all, void* stream) {
+    if (!frame || !weights || !z_all) return fail(DFN_E_ARG, "dfn_fine_depths: bad argument");
+    const DfnFrame& F = *frame;
+    if (counts_ok(F.n_coarse, F.n_fine, "dfn_fine_depths") != DFN_OK) return DFN_E_ARG;
+    if (F.n_fine == 0) return fail(DFN_E_ARG, "dfn_fine_depths: the frame has no fine pass (n_fine > 0 selects the pair)");
+    if (F.ray_count <= 0) return DFN_OK;
+    return launched(launch_fine_depths(weights, F.ray_count, F.n_coarse, F.n_fine, F.z_near, F.z_far, z_all, (hipStream_t)stream),
+                    "fine_depths_kernel");
 }
 
 // ---- training ---------------------------------------------------------------------------------------------------

@@ -43,6 +43,10 @@ constexpr int TIER_AUX = 0x400;
 // internal, the same way (dfn_render_rays_fwd / dfn_render_rays_fwd_u8 are entry points of their own): the instantiation that reads
 // its rays - origins, directions, optionally per-ray (near, far) - from memory instead of generating pinhole rays.  Never with TIER_AUX
 constexpr int TIER_RAYS = 0x800;
+// internal, the same way (dfn_render_z_fwd / dfn_render_z_fwd_u8 are entry points of their own): the instantiation that reads its
+// sample depths from memory instead of spacing them between near and far; coarse-only launches of 32 ... 192 samples.  Never with
+// TIER_AUX or TIER_RAYS
+constexpr int TIER_ZVALS = 0x1000;
 // a flag of the render variants (dfn_render_variant.hip) only - it never reaches a kernel's first template argument: the 16-bit
 // training forwards whose recorder writes e4m3 (render_kernel<.., ACT4 = false>: RenderArgs.act_e4m3)
 constexpr int TIER_E4M3 = 0x100;

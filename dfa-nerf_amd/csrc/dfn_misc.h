@@ -25,6 +25,8 @@ hipError_t launch_ndc_rays(int H, int W, float focal, float z_near, const float*
                            float* oo, float* od, hipStream_t st);
 hipError_t launch_sample_pdf(const float* bins, const float* weights, long R, int nb, int ns, const float* u,
                              float* out, hipStream_t st);
+hipError_t launch_fine_depths(const float* w, long R, int n_coarse, int n_fine, float z_near, float z_far, float* z_all,
+                              hipStream_t st);
 hipError_t launch_composite(const float* sigma, const float* feat, int K, long N, float* ssum, float* fw,
                             hipStream_t st);
 hipError_t launch_volume_weights(const float* z, const float* ray, const float* sigma, long R, int S,

@@ -431,6 +431,97 @@ hipError_t launch_sample_pdf(const float* bins, const float* weights, long R, in
     return hipGetLastError();
 }
 
+// ---- dfn_fine_depths: the fused renderer's fine sampler + merge on its own, one wavefront per ray ---------------------------------
+// The twin of what render_kernel (dfn_render_kernels.h) runs between its coarse and its fine passes, statement for statement - the
+// coarse depths from (z_near, z_far), sample_pdf(z_mid, w[1:-1], NF, det=True) with the butterfly sum and the double-precision scan,
+// searchsorted(right=True), the `denom < 1e-5` switch, then sort(cat(z, z_fine)) by ranks - so that, fed a coarse launch's weights, it
+// writes the z_all a hierarchical launch of the same tier writes, bit for bit (tests/test_gpu_zvals.py).  It is a copy and not a shared
+// device function: the render kernels' ISA stays what it was.  w: [R, NC] (w_head for one field, w_com for two); z_all: [R, NC + NF].
+__global__ __launch_bounds__(256) void fine_depths_kernel(const float* w, long R, int NC, int NF, float z_near, float z_far,
+                                                          float* z_all) {
+    __shared__ float zc_s[4][64], tmp_s[4][64], cdf_s[4][64], zf_s[4][128];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long ray = (long)blockIdx.x * 4 + wv;
+    if (ray >= R) return;                       // whole wave exits together
+    volatile float* zc = zc_s[wv];
+    volatile float* tmp = tmp_s[wv];
+    volatile float* cdf = cdf_s[wv];
+    volatile float* zf = zf_s[wv];
+    auto fence = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    if (lane < NC) {                            // coarse z: near*(1-t) + far*t, and the coarse weights
+        const float t = linspace01_(lane, NC);
+        zc[lane] = __fadd_rn(__fmul_rn(z_near, __fsub_rn(1.0f, t)), __fmul_rn(z_far, t));
+        tmp[lane] = w[ray * NC + lane];
+    }
+    fence();
+    const float wp = (lane >= 1 && lane <= NC - 2) ? __fadd_rn(tmp[lane], 1e-5f) : 0.f;
+    // sum(weights + 1e-5): element k (= coarse weight k + 1) in lane k, butterfly at XOR distances 32 ... 1
+    float Ssum = __shfl(wp, (lane + 1) & 63);
+#pragma unroll
+    for (int dlt = 32; dlt >= 1; dlt >>= 1) Ssum = __fadd_rn(Ssum, __shfl_xor(Ssum, dlt));
+    const float pdf = __fdiv_rn(wp, Ssum);
+    const float zmid = (lane < NC - 1) ? __fmul_rn(0.5f, __fadd_rn(zc[lane + 1], zc[lane])) : 0.f;
+    double c = (double)pdf;                     // torch.cumsum's double accumulator as a wave scan (exact: render_kernel)
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        const double up = __shfl_up(c, dlt);
+        if (lane >= dlt) c += up;
+    }
+    cdf[lane] = (lane <= NC - 2) ? (float)c : 3.0e38f;
+    fence();
+    tmp[lane] = zmid;                           // bins
+    fence();
+    for (int m = 0; m < (NF + 63) / 64; ++m) {
+        const int j = lane + 64 * m;
+        if (j >= NF) continue;
+        const float u = linspace01_(j, NF);
+        int inds = 0;                           // searchsorted(cdf[0..NC-2], u, right=True)
+#pragma unroll
+        for (int stp = 32; stp >= 1; stp >>= 1) {
+            const int t = inds + stp;
+            if (t <= NC - 1 && cdf[t - 1] <= u) inds = t;
+        }
+        const int below = max(inds - 1, 0), above = min(inds, NC - 2);
+        const float cb = cdf[below], ca = cdf[above];
+        const float bb = tmp[below], ba = tmp[above];
+        float den = __fsub_rn(ca, cb);
+        if (den < 1e-5f) den = 1.0f;
+        const float t = __fdiv_rn(__fsub_rn(u, cb), den);
+        zf[j] = __fadd_rn(bb, __fmul_rn(t, __fsub_rn(ba, bb)));
+    }
+    fence();
+    // z_all = sort(cat(z, z_fine)): ranks by counting (ties: coarse first, then fine in index order), no sortedness assumption
+    float* out = z_all + ray * (NC + NF);
+    if (lane < NC) {
+        const float myc = zc[lane];
+        int rank = lane;
+        for (int i = 0; i < NF; ++i) rank += (zf[i] < myc) ? 1 : 0;
+        out[rank] = myc;
+    }
+    for (int m = 0; m < (NF + 63) / 64; ++m) {
+        const int j = lane + 64 * m;
+        if (j >= NF) continue;
+        const float myf = zf[j];
+        int rank = 0;
+        for (int i = 0; i < NC; ++i) rank += (zc[i] <= myf) ? 1 : 0;
+        for (int i = 0; i < NF; ++i) {
+            const float v = zf[i];
+            rank += (v < myf || (v == myf && i < j)) ? 1 : 0;
+        }
+        out[rank] = myf;
+    }
+}
+hipError_t launch_fine_depths(const float* w, long R, int n_coarse, int n_fine, float z_near, float z_far, float* z_all,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(fine_depths_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, w, R, n_coarse, n_fine, z_near, z_far,
+                       z_all);
+    return hipGetLastError();
+}
+
 // ---- composite_function ------------------------------------------------------------------------------------------------
 __global__ void composite_kernel(const float* sigma, const float* feat, int K, long N, float* ssum, float* fw) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

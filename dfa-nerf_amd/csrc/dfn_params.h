@@ -31,7 +31,10 @@ struct RenderArgs {
     // (rays launch - inference, so the recorder is off: `bounds`, optional f32 [ray_count,2] = (near, far) per ray; NULL = frame.z_near / z_far)
     union { float* samples_out; const float* bounds; };         // [ray_count][n_coarse + n_fine][8], evaluation order (coarse points, then the fine ones)
     // hierarchical training: [ray_count][n_coarse + n_fine] merged rank of every evaluated point (aux launch, u8 route: depth16_com)
-    union { unsigned char* ranks_out; unsigned short* depth16_com; };
+    // (z launch - inference without a fine pass, so no ranks, and never aux: `zvals`, f32 [ray_count][n_coarse], the sample depths of ray r
+    // in the launch's ray order, non-decreasing.  Non-null in a launch that records nothing and is not aux = the z instantiation,
+    // render_kernel<TW | TIER_ZVALS>: host-side dispatch reads the pointer, dfn_render.hip)
+    union { unsigned char* ranks_out; unsigned short* depth16_com; const float* zvals; };
     void* act_T[2];
     unsigned* masks[2];
     long NP;

@@ -1,5 +1,5 @@
 // dfn_render_kernels.h - fused frame renderer and fused decoder for gfx950 (MI355X): the kernel templates.
-// Instantiated per render variant - a precision tier and a set of flags (width, aux, rays) - each an object of its own, all from one
+// Instantiated per render variant - a precision tier and a set of flags (width, aux, rays, zvals) - each an object of its own, all from one
 // source: dfn_render_variant.hip, whose header describes the scheme; dfn_render.hip dispatches on the tier, the width and the
 // aux / rays switches.
 //
@@ -160,6 +160,13 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // depths, in place of F.z_near / F.z_far.  The background is indexed by the ray (bg[r]); there is no pixel id.  Only the "this
 // wave's ray" block differs: the ray still lives in the LDS state, so nothing new is live across an MLP pass, and everything
 // after that block - coarse loop, sampler, merge, fine passes, compositing, per-sample outputs, epilogues - is the same code.
+// TIER_ZVALS in TW (inference only, never with TIER_AUX or TIER_RAYS): the wave's sample depths are read from memory instead of being
+// spaced between near and far (include/dfanerf.h, dfn_render_z_fwd).  Row r of A.zvals is the NC non-decreasing depths of the launch's
+// ray r - the row index of the outputs, not the pixel id.  The launch is coarse-only (n_fine == 0) with NC = 32 ... 192 in steps of 32:
+// zall holds 192 floats, the coarse loop and the per-sample outputs are general in NC / 32, and the two-field weight schedule is
+// built for KC = NC / 32 <= 6 tiles here (the plain kernels' constant covers the 4 they can have).  Only the "this wave's ray" block
+// differs otherwise: everything after it - tiles, integrate_tile, dz = z[i + 1] - z[i], last_dist and the background plane on the
+// last sample, w_head / w_com / z_out, both epilogues - is the same code.
 template <int TW, bool TWO, int TRAIN, bool ACT4 = true>
 __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & TIER_MASK)>::THREADS / 256) void render_kernel(
     const RenderArgs A) {
@@ -170,6 +177,9 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     constexpr bool RAYS = (TW & TIER_RAYS) != 0;
     static_assert(!RAYS || TRAIN == 0, "caller-supplied rays are inference only");
     static_assert(!RAYS || !AUX, "no aux form for caller-supplied rays");
+    constexpr bool ZVALS = (TW & TIER_ZVALS) != 0;
+    static_assert(!ZVALS || TRAIN == 0, "caller-supplied depths are inference only");
+    static_assert(!ZVALS || (!AUX && !RAYS), "no aux and no rays form for caller-supplied depths");
     using C = TierCfg<TIER>;
     using L = KernelLds<TIER, TWO>;
     using P = Prog<TIER, HT>;
@@ -216,7 +226,8 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     s.nslab1 = A.nslab[1];
     // coarse: H T per coarse tile (NC / 32 of them: H T H T for the scripts' 64); fine: KF x H, then KF x T
     const int KC = NC / 32;
-    s.sched = two ? ((0xAAu & ((1u << (2 * KC)) - 1u)) | (((1u << KF) - 1u) << (2 * KC + KF))) : 0u;
+    if constexpr (ZVALS) s.sched = two ? (0xAAAu & ((1u << (2 * KC)) - 1u)) : 0u;      // (H T) x KC, KC <= 6; no fine pass
+    else s.sched = two ? ((0xAAu & ((1u << (2 * KC)) - 1u)) | (((1u << KF) - 1u) << (2 * KC + KF))) : 0u;
 #ifdef DFN_TIMING
     s.t_wait = s.t_bar = s.t_issue = 0;
     unsigned long long T_mlp = 0, T_pdf = 0;
@@ -306,9 +317,15 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             for (int k = 0; k < 3; ++k) st[RS_RGB_H + k] = st[RS_RGB_C + k] = 0.f;
         }
         // coarse z: near*(1-t) + far*t (run_nerf_com_trainExpLater.py:617-618)
-        for (int i = lane; i < NC; i += 64) {
-            const float t = linspace01(i, NC);
-            zall[i] = add_(mul_(z_near, sub_(1.0f, t)), mul_(z_far, t));
+        if constexpr (ZVALS) {
+            // (32-bit byte offsets: wave-uniform base + lane offset; the API holds ray_count * n_coarse under 2^30 for a z launch)
+            for (int i = lane; i < NC; i += 64)
+                zall[i] = *(const float*)((const char*)A.zvals + ((unsigned)r * (unsigned)NC + (unsigned)i) * 4u);
+        } else {
+            for (int i = lane; i < NC; i += 64) {
+                const float t = linspace01(i, NC);
+                zall[i] = add_(mul_(z_near, sub_(1.0f, t)), mul_(z_far, t));
+            }
         }
     }
     __syncthreads();     // bias blob + ray state visible (also drains the first two slab loads)
@@ -466,9 +483,18 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             if (hier) {
                 if (lane < 32) tmp[si] = two ? w_c : w_h;
             } else if (!AUX && valid && lane < 32) {
-                if (A.w_head) A.w_head[(size_t)r_raw * NC + si] = w_h;
-                if (A.w_com && two) A.w_com[(size_t)r_raw * NC + si] = w_c;
-                if (A.z_out) A.z_out[(size_t)r_raw * NC + si] = z;
+                if constexpr (ZVALS) {
+                    // one 32-bit byte offset serves the three arrays (ray_count * n_coarse < 2^30, as above): no per-lane 64-bit
+                    // address is kept across the MLP passes - the f16 kernels have no register to spare for one
+                    const unsigned off = ((unsigned)r_raw * (unsigned)NC + (unsigned)si) * 4u;
+                    if (A.w_head) *(float*)((char*)A.w_head + off) = w_h;
+                    if (A.w_com && two) *(float*)((char*)A.w_com + off) = w_c;
+                    if (A.z_out) *(float*)((char*)A.z_out + off) = z;
+                } else {
+                    if (A.w_head) A.w_head[(size_t)r_raw * NC + si] = w_h;
+                    if (A.w_com && two) A.w_com[(size_t)r_raw * NC + si] = w_c;
+                    if (A.z_out) A.z_out[(size_t)r_raw * NC + si] = z;
+                }
             }
             if (++tile < NC / 32) continue;
             if (!hier) break;
@@ -864,7 +890,7 @@ template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true, int W128 = 0> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
-    static_assert((W128 & ~(TIER_W128 | TIER_AUX | TIER_RAYS)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux / rays: inference only");      // (W128 also carries TIER_AUX / TIER_RAYS)
+    static_assert((W128 & ~(TIER_W128 | TIER_AUX | TIER_RAYS | TIER_ZVALS)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux / rays / zvals: inference only");      // (W128 also carries TIER_AUX / TIER_RAYS / TIER_ZVALS)
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER, TWO>::TOTAL;
     static bool attr_done = false;
@@ -897,7 +923,8 @@ template <int TIER, bool TORSO, bool REC = false, int W128 = 0> static hipError_
 // and, in a trainable tier, the training forwards (recorder on).  Every other variant is inference only and holds the kernels of its
 // flags alone: TIER_W128 (the API refuses DFN_WIDTH_128 in every training entry point), TIER_AUX (dfn_render_fwd_aux /
 // dfn_render_fwd_u8_aux), TIER_RAYS (dfn_render_rays_fwd / dfn_render_rays_fwd_u8; the recorder's samples_out slot carries `bounds`),
-// the last two with or without TIER_W128.  TIER_E4M3: the two 16-bit training forwards whose recorder writes act_T as MX-fp8 e4m3
+// TIER_ZVALS (dfn_render_z_fwd / dfn_render_z_fwd_u8; the recorder's ranks_out slot carries `zvals`), the last three with or without
+// TIER_W128.  TIER_E4M3: the two 16-bit training forwards whose recorder writes act_T as MX-fp8 e4m3
 // (the run-time opt-out of the narrow activation format, for A/B runs of the two formats on real data in one process), nothing else.
 template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st) {
     if constexpr (FLAGS == TIER_E4M3) {
@@ -905,6 +932,8 @@ template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A
     } else {
         if constexpr ((FLAGS & TIER_RAYS) != 0) {
             if (!A.use_rays || A.aux || !A.rays) return hipErrorInvalidValue;
+        } else if constexpr ((FLAGS & TIER_ZVALS) != 0) {
+            if (A.samples_out || A.aux || A.use_rays || !A.zvals || A.frame.n_fine != 0) return hipErrorInvalidValue;
         } else if constexpr ((FLAGS & TIER_AUX) != 0) {
             if (A.samples_out || !A.aux) return hipErrorInvalidValue;
         } else if (A.samples_out) {     // training step: two fields, recorder on; coarse only (MAIN:855-899) or hierarchical (row H)

@@ -14,6 +14,7 @@
 //   TIER_W128              the 128-wide inference program (DFN_WIDTH_128; Prog<TIER, HT = 4>): render and decoder, inference only
 //   [TIER_W128 |] TIER_AUX   the render kernels that also write opacity and expected depth (RenderArgs.aux): render only
 //   [TIER_W128 |] TIER_RAYS  the render kernels for caller-supplied rays (RenderArgs.use_rays): render only
+//   [TIER_W128 |] TIER_ZVALS the render kernels for caller-supplied sample depths (RenderArgs.zvals; coarse-only, 32 ... 192 samples): render only
 //   TIER_E4M3              bf16 only: the two training forwards whose recorder writes act_T as MX-fp8 e4m3
 // The flagged variants exist for the inference tiers (f32, f16, f16x3); bf16 is the training tier.
 //

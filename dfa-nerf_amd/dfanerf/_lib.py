@@ -73,6 +73,9 @@ def _load():
         "dfn_render_fwd_u8_aux": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
         "dfn_render_rays_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, fp, fp, fp, fp, fp, vp]),
         "dfn_render_rays_fwd_u8": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, vp, vp, vp]),
+        "dfn_render_z_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, fp, fp, fp, vp]),
+        "dfn_render_z_fwd_u8": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, vp, vp, fp, vp]),
+        "dfn_fine_depths": (i32, [C.POINTER(DfnFrame), fp, fp, vp]),
         "dfn_decoder_fwd": (i32, [i32, i32, vp, fp, fp, fp, lg, fp, fp, vp]),
         "dfn_decoder_train_fwd": (i32, [i32, i32, vp, fp, fp, fp, lg, fp, fp, fp, vp, vp, vp]),
         "dfn_get_rays": (i32, [i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), fp, fp, vp]),

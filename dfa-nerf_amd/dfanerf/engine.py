@@ -387,6 +387,26 @@ def _rays_inputs(who, packed, frame, bg, rays, bounds, **refused):
     return _f32c(rays, packed.device), bounds
 
 
+Z_COARSE = (32, 64, 96, 128, 160, 192)      # sample counts of a z launch (dfn_render_z_fwd): every multiple of 32 the kernel's LDS holds
+
+
+def _z_inputs(who, packed, frame, z_vals, **refused):
+    """checks of a z launch (dfn_render_z_fwd[_u8]) -> z_vals as a contiguous f32 device tensor [ray_count, n_coarse]"""
+    for name, v in refused.items():
+        if v is not None and v is not False:
+            raise ValueError(f"{who}: z_vals cannot be combined with {name} ("
+                             + ("supplied rays bring their own depth range (bounds); there is no rays form of dfn_render_z_fwd"
+                                if name in ("rays", "bounds") else "there is no opacity / depth form of dfn_render_z_fwd") + ")")
+    if frame.n_fine != 0 or frame.n_coarse not in Z_COARSE:
+        raise ValueError(f"{who}: with z_vals the frame has n_fine == 0 and n_coarse = the depths per ray, a multiple of 32 in 32 ... 192 "
+                         f"(got {frame.n_coarse} + {frame.n_fine})")
+    z_vals = torch.as_tensor(z_vals)
+    if tuple(z_vals.shape) != (frame.ray_count, frame.n_coarse):
+        raise ValueError(f"{who}: z_vals must be [ray_count, n_coarse] = [{frame.ray_count}, {frame.n_coarse}] (row r: the depths of the "
+                         f"launch's ray r, non-decreasing), got {tuple(z_vals.shape)}")
+    return _f32c(z_vals, packed.device)
+
+
 def _launch_inputs(who, dtype, packed, bias, frame, bg, pix_index, out_head, out_com):
     """What every dfn_render* entry point takes, for render() (dtype float32) and render_u8() (uint8) ->
     (net, bgs, pix_index, out_head, out_com): net = the leading arguments (tier, frame, packed head, packed torso, bias, bias_t),
@@ -409,7 +429,7 @@ def _launch_inputs(who, dtype, packed, bias, frame, bg, pix_index, out_head, out
 
 
 def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head=None, out_com=None, want_z=False,
-           want_aux=False, rays=None, bounds=None):
+           want_aux=False, rays=None, bounds=None, z_vals=None):
     """dfn_render_fwd.  bg: f32 [H*W,3] in [0,1] or uint8 [H*W,3] device tensor.
     Returns (rgb_head [n,3], rgb_com [n,3] or None[, w_head, w_com][, z_vals][, aux_head, aux_com]).
     want_aux: dfn_render_fwd_aux - aux_head / aux_com [n,2] = (acc, depth): opacity and premultiplied expected depth of each image
@@ -418,7 +438,12 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     rays: dfn_render_rays_fwd - render these rays instead of the frame's pinhole rays: float32 [ray_count, 6 * fields] from
     pack_rays(); bg is then [ray_count, 3] (row r: the background of ray r) and frame.ray_count must equal the row count (H, W, the
     intrinsics, the poses and ray_begin of the frame are ignored).  bounds: optional [ray_count, 2] = (near, far) per ray, in place
-    of frame.z_near / z_far.  want_weights / want_z work; pix_index and want_aux do not (ValueError)."""
+    of frame.z_near / z_far.  want_weights / want_z work; pix_index and want_aux do not (ValueError).
+    z_vals: dfn_render_z_fwd - render at these depths instead of the frame's linspace: float32 [ray_count, n_coarse], row r the
+    non-decreasing depths of the launch's ray r (the row index of the outputs, not the pixel id); the frame has n_fine == 0 and
+    n_coarse = 32 ... 192 in steps of 32.  pix_index, want_weights and want_z work; rays and want_aux do not (ValueError)."""
+    if z_vals is not None:
+        z_vals = _z_inputs("render", packed, frame, z_vals, rays=rays, bounds=bounds, want_aux=want_aux)
     if rays is None and bounds is not None:
         raise ValueError("render: bounds are per-ray depth ranges of supplied rays (rays=)")
     if rays is not None:
@@ -441,6 +466,8 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
     outs = (_ptr(rgb_h), _ptr(rgb_c), _ptr(w_h), _ptr(w_c), _ptr(z_v), _stream())
     if rays is not None:
         check(lib.dfn_render_rays_fwd(*net, _ptr(rays), _ptr(bounds), *bgs, *outs), "dfn_render_rays_fwd")
+    elif z_vals is not None:
+        check(lib.dfn_render_z_fwd(*net, *bgs, _ptr(pix_index), *outs[:-1], _ptr(z_vals), _stream()), "dfn_render_z_fwd")
     else:
         check(lib.dfn_render_fwd(*net, *bgs, _ptr(pix_index), *outs), "dfn_render_fwd")
     out = (rgb_h, rgb_c)
@@ -452,12 +479,15 @@ def render(packed, bias, frame, bg, pix_index=None, want_weights=False, out_head
 
 
 def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=None, want_alpha=False, want_depth=False,
-              rays=None, bounds=None):
+              rays=None, bounds=None, z_vals=None):
     """dfn_render_fwd_u8: the same launch with to8b fused into the epilogue -> uint8 [n,3] images (head, composite).
     want_alpha / want_depth: dfn_render_fwd_u8_aux - the return value grows by (alpha8_head, alpha8_com) uint8 [n] and / or
     (depth16_head, depth16_com) uint16 [n], in this order (the _com entries None with one field); include/dfanerf.h has the
     formulas.  Without them the plain entry point is the one called.
-    rays / bounds: dfn_render_rays_fwd_u8 - as in render(); not together with pix_index / want_alpha / want_depth (ValueError)."""
+    rays / bounds: dfn_render_rays_fwd_u8 - as in render(); not together with pix_index / want_alpha / want_depth (ValueError).
+    z_vals: dfn_render_z_fwd_u8 - as in render(); not together with rays / want_alpha / want_depth (ValueError)."""
+    if z_vals is not None:
+        z_vals = _z_inputs("render_u8", packed, frame, z_vals, rays=rays, bounds=bounds, want_alpha=want_alpha, want_depth=want_depth)
     if rays is None and bounds is not None:
         raise ValueError("render_u8: bounds are per-ray depth ranges of supplied rays (rays=)")
     if rays is not None:
@@ -480,9 +510,77 @@ def render_u8(packed, bias, frame, bg, pix_index=None, out_head=None, out_com=No
         return out
     if rays is not None:
         check(lib.dfn_render_rays_fwd_u8(*net, _ptr(rays), _ptr(bounds), *bgs, _ptr(out_h), _ptr(out_c), _stream()), "dfn_render_rays_fwd_u8")
+    elif z_vals is not None:
+        check(lib.dfn_render_z_fwd_u8(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), _ptr(z_vals), _stream()), "dfn_render_z_fwd_u8")
     else:
         check(lib.dfn_render_fwd_u8(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), _stream()), "dfn_render_fwd_u8")
     return out_h, out_c
+
+
+def fine_depths(frame, weights, out=None):
+    """dfn_fine_depths: the fused renderer's fine sampler + merge on its own.  weights [ray_count, n_coarse]: the coarse weights of a
+    coarse-only launch at frame.n_coarse (w_head for one field, w_com for two); frame.n_fine > 0 selects the pair.  -> z_all
+    [ray_count, n_coarse + n_fine], the sorted depths a hierarchical launch of the same tier renders at (bit for bit)."""
+    n, S = frame.ray_count, frame.n_coarse + frame.n_fine
+    if tuple(weights.shape) != (n, frame.n_coarse):
+        raise ValueError(f"fine_depths: weights must be [ray_count, n_coarse] = [{n}, {frame.n_coarse}], got {tuple(weights.shape)}")
+    w = _f32c(weights, weights.device)
+    if out is None:
+        out = torch.empty(n, S, dtype=torch.float32, device=w.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, S):
+        raise ValueError(f"fine_depths: out must be contiguous float32 [{n}, {S}]")
+    check(lib.dfn_fine_depths(C.byref(frame), _ptr(w), _ptr(out), _stream()), "dfn_fine_depths")
+    return out
+
+
+def two_pass_workspace(packed, frame):
+    """The intermediate buffers of one render_two_pass call for `frame` (ray_count, n_coarse + n_fine, fields) on packed.device: pass A's
+    images, the coarse weights and the merged depths.  A caller that renders many frames of one size allocates it once and passes it
+    as `workspace=`; it belongs to one stream at a time."""
+    dev, n, two = packed.device, frame.ray_count, frame.fields == 2
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return {"rgb_h": f32(n, 3), "rgb_c": f32(n, 3) if two else None, "w": f32(n, frame.n_coarse), "z": f32(n, frame.n_coarse + frame.n_fine)}
+
+
+def render_two_pass(packed_sampler, bias_sampler, packed, bias, frame, bg, pix_index=None, u8=False, out_head=None, out_com=None,
+                    workspace=None, want_z=False):
+    """The hierarchical render of `frame` (n_coarse + n_fine) in two launches with the sampler between them: pass A renders the
+    n_coarse coarse samples with `packed_sampler` for their weights, dfn_fine_depths turns them into the merged depths, pass B renders
+    those n_coarse + n_fine depths with `packed` (dfn_render_z_fwd[_u8]) - one tier places the fine samples, another renders them.
+    Three launches on the current stream, no host synchronisation and no other kernel between them.  workspace: the intermediate
+    buffers from two_pass_workspace() for this frame size, owned by the caller; None allocates them for this call (torch's caching
+    allocator: no kernel, no synchronisation, and blocks are handed out per stream).
+    -> (rgb_head, rgb_com or None) float32, uint8 with u8[, z_all [ray_count, n_coarse + n_fine] with want_z: the workspace's depth
+    buffer - the caller's own, or this call's]."""
+    dev, n, two = packed.device, frame.ray_count, frame.fields == 2
+    NC, NF = frame.n_coarse, frame.n_fine
+    if NF <= 0:
+        raise ValueError("render_two_pass: the frame has no fine pass (n_fine == 0): render() is the one-launch call")
+    if pix_index is not None:
+        pix_index = pix_index.to(device=dev, dtype=torch.int32).contiguous()
+    buf = two_pass_workspace(packed, frame) if workspace is None else workspace
+    if tuple(buf["w"].shape) != (n, NC) or tuple(buf["z"].shape) != (n, NC + NF) or (buf["rgb_c"] is None) == two:
+        raise ValueError(f"render_two_pass: the workspace is not this frame's ({n} rays, {NC} + {NF} samples, fields == {frame.fields}): "
+                         "two_pass_workspace(packed, frame)")
+    fr_a, fr_b = DfnFrame.from_buffer_copy(frame), DfnFrame.from_buffer_copy(frame)
+    fr_a.n_fine = 0
+    fr_b.n_coarse, fr_b.n_fine = NC + NF, 0
+    # (pass A's images are written and never read: the render kernels have no weights-only form - rgb_head is a required output, and
+    # the colour sums are 12 bytes per ray next to the 4 n_coarse of the weights)
+    net, bgs, _, _, _ = _launch_inputs("render_two_pass", torch.float32, packed_sampler, bias_sampler, fr_a, bg, None, buf["rgb_h"],
+                                       buf["rgb_c"])
+    check(lib.dfn_render_fwd(*net, *bgs, _ptr(pix_index), _ptr(buf["rgb_h"]), _ptr(buf["rgb_c"]), None if two else _ptr(buf["w"]),
+                             _ptr(buf["w"]) if two else None, None, _stream()), "dfn_render_fwd (two-pass: coarse)")
+    check(lib.dfn_fine_depths(C.byref(frame), _ptr(buf["w"]), _ptr(buf["z"]), _stream()), "dfn_fine_depths")
+    dtype = torch.uint8 if u8 else torch.float32
+    net, bgs, _, out_h, out_c = _launch_inputs("render_two_pass", dtype, packed, bias, fr_b, bg, None, out_head, out_com)
+    if u8:
+        check(lib.dfn_render_z_fwd_u8(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), _ptr(buf["z"]), _stream()),
+              "dfn_render_z_fwd_u8")
+    else:
+        check(lib.dfn_render_z_fwd(*net, *bgs, _ptr(pix_index), _ptr(out_h), _ptr(out_c), None, None, None, _ptr(buf["z"]), _stream()),
+              "dfn_render_z_fwd")
+    return (out_h, out_c, buf["z"]) if want_z else (out_h, out_c)
 
 
 def decoder_forward(packed, field, bias, points, dirs):

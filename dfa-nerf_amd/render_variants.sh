@@ -23,6 +23,12 @@ f16x3_rays      TIER_F16X3  TIER_RAYS
 f32_w128_rays   TIER_F32    TIER_W128|TIER_RAYS
 f16_w128_rays   TIER_F16    TIER_W128|TIER_RAYS
 f16x3_w128_rays TIER_F16X3  TIER_W128|TIER_RAYS
+f32_z           TIER_F32    TIER_ZVALS
+f16_z           TIER_F16    TIER_ZVALS
+f16x3_z         TIER_F16X3  TIER_ZVALS
+f32_w128_z      TIER_F32    TIER_W128|TIER_ZVALS
+f16_w128_z      TIER_F16    TIER_W128|TIER_ZVALS
+f16x3_w128_z    TIER_F16X3  TIER_W128|TIER_ZVALS
 "
 # variant_units [tier ...]: the unit names (dfn_render_<name>) of the variants of these tiers, or of all of them
 variant_units() {

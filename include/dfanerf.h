@@ -68,7 +68,9 @@ extern "C" {
 const char* dfn_last_error(void);
 /* library build info: "dfanerf <version> gfx950".  ABI notes - 0.4: + dfn_render_fwd_aux, dfn_render_fwd_u8_aux (per-ray opacity and
  * expected depth next to the RGB; inference tiers, both widths; nothing else changes); + dfn_render_rays_fwd, dfn_render_rays_fwd_u8
- * (the fused renderer on caller-supplied rays; inference tiers, both widths; nothing else changes, the version string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * (the fused renderer on caller-supplied rays; inference tiers, both widths; nothing else changes, the version string stays);
+ * + dfn_render_z_fwd, dfn_render_z_fwd_u8 (the fused renderer at caller-supplied sample depths, 32 ... 192 per ray) and dfn_fine_depths
+ * (the fused fine sampler + merge on its own); inference tiers, both widths; nothing else changes, the version string stays.  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -241,6 +243,43 @@ int dfn_render_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head
 int dfn_render_rays_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                            const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
                            const float* bg_f32, const uint8_t* bg_u8, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream);
+
+/* The fused renderer at CALLER-SUPPLIED sample depths: dfn_render_fwd with the depths of MAIN:617-619 (z_vals = near * (1 - t) +
+ * far * t, the same for every ray) replaced by data, then the reference's renderer on them unchanged - points, decoder, background
+ * and sigma fix-ups, composite, weights (MAIN:653-709).  The NeRF lineage's render_rays(ray_batch, z_vals); the counterpart of the
+ * oracle's render_fixed_samples.
+ *   zvals   f32 [ray_count, n_coarse], required.  Row r = the depths of the launch's ray r - the row index of the outputs (with
+ *           pix_index: of pix_index[r]), NOT the pixel id - non-decreasing; equal neighbours are allowed (a zero-length interval has
+ *           alpha = 1 - exp(0) = 0 and gets no weight).  The distance behind the last depth is frame.last_dist, and with
+ *           concate_bg the last depth carries the background plane, as in dfn_render_fwd.
+ * Sample counts - this entry point's own rule: frame.n_fine == 0 and frame.n_coarse (the depths per ray) a multiple of 32 in
+ * 32 ... 192; anything else is DFN_E_ARG before any device work, whatever the ray count.  frame.z_near / z_far are not used.
+ * Every other argument, output (weights_* / z_vals [ray_count, n_coarse]; z_vals returns the depths read) and check:
+ * dfn_render_fwd's.  Fed the z_vals output of a coarse-only dfn_render_fwd launch (n_coarse 32 / 64 / 128), every output equals that
+ * launch's bit for bit: the kernels differ in where the depths come from, nothing else.
+ * Tiers DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3, with or without DFN_WIDTH_128.  DFN_E_ARG with a message, before any device
+ * work: zvals == NULL; DFN_TIER_BF16 (the training tier).  There is NO aux form, NO rays form and NO training form. */
+int dfn_render_z_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                     const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                     const int32_t* pix_index, float* rgb_head, float* rgb_com, float* weights_head, float* weights_com,
+                     float* z_vals, const float* zvals, void* stream);
+/* ... with to8b fused into the epilogue, as dfn_render_fwd_u8: rgb8_* [ray_count,3] uint8.  Stands for the same lines,
+ * MAIN:617-619 and MAIN:653-709, then MAIN:712-732. */
+int dfn_render_z_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                        const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
+                        const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, const float* zvals, void* stream);
+
+/* The fused renderer's fine sampler + merge as a call of its own: what dfn_render_fwd computes between its coarse and its fine
+ * pass - sample_pdf(z_mid, weights[1:-1], n_fine, det=True) (HELP:537-581: weights + 1e-5, pdf, cumsum,
+ * searchsorted(right=True), the `denom < 1e-5` switch, the lerp) on the frame's coarse depths (MAIN:617-619 from z_near / z_far), then
+ * sort(cat(z, z_fine)) - in the fused kernel's arithmetic: the sum of the weights by a butterfly over the wave, the cumulative sum in
+ * double precision, ties of the merge resolved coarse first.
+ *   weights f32 [ray_count, n_coarse]: the coarse weights - weights_head of a coarse-only launch for one field, weights_com for two
+ *   z_all   f32 [ray_count, n_coarse + n_fine]: the merged depths, non-decreasing
+ * Frame fields used: ray_count, n_coarse, n_fine (a pair the forward entry points take with n_fine > 0), z_near, z_far.  Fed the
+ * coarse weights of tier T, z_all is the z_vals output of tier T's hierarchical dfn_render_fwd launch bit for bit.  With
+ * dfn_render_z_fwd it splits that launch in two, so that one tier can place the fine samples and another render them. */
+int dfn_fine_depths(const DfnFrame* frame, const float* weights, float* z_all, void* stream);
 
 /* ---- training step: replaces loss.backward() through MAIN:855-899 + DEC:277-349 (torch autograd upstream) ------
  * One step = dfn_train_fwd (the fused renderer with its recorder on: coarse samples, both fields) ->

@@ -49,11 +49,12 @@ def main(paths):
                   + ("" if ok else "   <-- FAIL"))
             bad += not ok
     # (an _aux unit - dfn_render_<tier>[_w128]_aux.hip, the kernels that also write opacity and depth - holds two render kernels only;
-    # so does a _rays unit - dfn_render_<tier>[_w128]_rays.hip, the kernels for caller-supplied rays)
-    want = 2 if all("_aux-hip-" in p or "_rays-hip-" in p for p in paths) else 4
+    # so does a _rays unit - dfn_render_<tier>[_w128]_rays.hip, the kernels for caller-supplied rays - and a _z unit -
+    # dfn_render_<tier>[_w128]_z.hip, the kernels for caller-supplied depths)
+    want = 2 if all("_aux-hip-" in p or "_rays-hip-" in p or "_z-hip-" in p for p in paths) else 4
     if any("dfn_render_f16" in p or p.endswith("dfn_render_bf16-hip-amdgcn-amd-amdhsa-gfx950.s") for p in paths) and seen < want:
         print(f"check_scratch: only {seen} inference kernels recognised (expected 2 render + 2 decoder per 16-bit unit, 2 render per "
-              "_aux / _rays unit): the name patterns are out of date   <-- FAIL")
+              "_aux / _rays / _z unit): the name patterns are out of date   <-- FAIL")
         return 1
     return 1 if bad else 0
 
