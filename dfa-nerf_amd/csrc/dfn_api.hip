@@ -643,13 +643,31 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
                           const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                           const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                           uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all, uint8_t* ranks,
-                          bool hier, void* stream, const DfnTrainLoss* loss = nullptr, bool with_loss = false) {
-    const char* who = hier ? "dfn_train_fwd_hier" : "dfn_train_fwd";
+                          bool hier, void* stream, const DfnTrainLoss* loss = nullptr, bool with_loss = false,
+                          const RaysIn* rin = nullptr) {
+    // rin: the step on caller-supplied rays (dfn_train_rays_fwd / _hier; no pixel ids, no _loss form)
+    const char* who = rin ? (hier ? "dfn_train_rays_fwd_hier" : "dfn_train_rays_fwd") : hier ? "dfn_train_fwd_hier" : "dfn_train_fwd";
     // the format flag rides in the tier argument (include/dfanerf.h: DFN_TRAIN_ACT_E4M3); 16-bit tier only
     if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;
     const int act_e4m3 = (tier & DFN_TRAIN_ACT_E4M3) != 0;
     if (tier >= 0) tier &= ~DFN_TRAIN_ACT_E4M3;
     if (act_e4m3 && tier != DFN_TIER_BF16) return fail(DFN_E_ARG, std::string(who) + ": DFN_TRAIN_ACT_E4M3 applies to DFN_TIER_BF16 only");
+    if (rin) {
+        if (!rin->rays)
+            return fail(DFN_E_ARG, std::string(who) + ": rays is NULL (" + (hier ? "dfn_train_fwd_hier" : "dfn_train_fwd") +
+                                       " renders the frame's own pinhole rays)");
+        if (tier == DFN_TIER_F16 || tier == DFN_TIER_F16X3)
+            return fail(DFN_E_ARG, std::string(who) + ": DFN_TIER_F16 / DFN_TIER_F16X3 are inference only; the training step runs in "
+                                                      "DFN_TIER_F32 / DFN_TIER_BF16");
+        if (frame && frame->fields != 2)
+            return fail(DFN_E_ARG, std::string(who) + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, "
+                                                      "o_torso, d_torso)");
+        if (frame && !hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
+            return fail(DFN_E_ARG, std::string(who) + ": 32, 64 or 128 coarse samples, no fine ones (dfn_train_rays_fwd_hier is the "
+                                                      "hierarchical variant)");
+        if (frame && hier && frame->n_fine == 0)
+            return fail(DFN_E_ARG, std::string(who) + ": n_fine > 0 (dfn_train_rays_fwd is the coarse-only step)");
+    }
     if (with_loss && (!loss || !loss->img_head || !loss->img_com || !loss->d_rgb_head || !loss->d_rgb_com || !loss->losses ||
                       !loss->workspace))
         return fail(DFN_E_ARG, std::string(who) + "_loss: bad loss argument");
@@ -684,6 +702,11 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
     A.NP = NP;
     A.act_e4m3 = act_e4m3;
     if (with_loss) A.loss = *loss;
+    if (rin) {       // the recorder owns samples_out: the bounds ride in the w_head slot, which a training launch leaves null (dfn_params.h)
+        A.use_rays = 2;
+        A.rays = rin->rays;             // (the pix_index slot)
+        A.train_bounds = rin->bounds;
+    }
     return launched(launch_render(tier, A, (hipStream_t)stream), "render_kernel(train)");
 }
 
@@ -724,6 +747,25 @@ int dfn_train_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head,
                           rgb_com, samples, act_head, masks_head, act_torso, masks_torso, z_all, ranks, true, stream);
 }
 
+int dfn_train_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                       const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                       const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples, void* act_head,
+                       uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head, rgb_com,
+                          samples, act_head, masks_head, act_torso, masks_torso, nullptr, nullptr, false, stream, nullptr, false, &rin);
+}
+
+int dfn_train_rays_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                            const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                            const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples,
+                            void* act_head, uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all,
+                            uint8_t* ranks, void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head, rgb_com,
+                          samples, act_head, masks_head, act_torso, masks_torso, z_all, ranks, true, stream, nullptr, false, &rin);
+}
+
 int dfn_sample_pixels(int H, int W, int n, int rect_num, const int32_t* rect, uint64_t seed, uint64_t counter,
                       int32_t* pix_index, int32_t* status, void* stream) {
     if (H <= 0 || W <= 0 || n <= 0 || rect_num < 0 || rect_num > n || !pix_index || (rect_num > 0 && !rect))
@@ -743,8 +785,16 @@ int dfn_mse_loss_u8(const float* rgb_head, const float* rgb_com, const uint8_t* 
 
 static int composite_bwd_impl(bool hier, const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                               const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
-                              const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream) {
-    const std::string who = hier ? "dfn_composite_bwd_hier" : "dfn_composite_bwd";
+                              const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream,
+                              const RaysIn* rin = nullptr) {
+    // rin: the step on caller-supplied rays (dfn_composite_bwd_rays_z / _hier_rays_z; no pixel ids)
+    const std::string who = rin ? (hier ? "dfn_composite_bwd_hier_rays_z" : "dfn_composite_bwd_rays_z") : hier ? "dfn_composite_bwd_hier" : "dfn_composite_bwd";
+    if (rin && !rin->rays)
+        return fail(DFN_E_ARG, who + ": rays is NULL (" + (hier ? "dfn_composite_bwd_hier_z" : "dfn_composite_bwd_z") +
+                                   " rebuilds the frame's own pinhole rays)");
+    if (rin && zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
+    if (rin && frame && frame->fields != 2)
+        return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
     if (!frame || !samples || (hier && (!z_all || !ranks)) || !d_rgb_head || !dsamples || (!bg_f32 && !bg_u8))
         return fail(DFN_E_ARG, who + ": bad argument");
     if (hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
@@ -752,7 +802,7 @@ static int composite_bwd_impl(bool hier, const DfnFrame* frame, const int32_t* p
     if (!hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
         return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (dfn_composite_bwd_hier)");
     if (frame->ray_count <= 0) return DFN_OK;
-    CompositeBwdArgs A{};
+    CompositeBwdRaysArgs A{};           // (the plain launches take its base: the block they have always had)
     A.frame = *frame;
     A.pix_index = pix_index;
     A.bg_f32 = bg_f32;
@@ -765,6 +815,11 @@ static int composite_bwd_impl(bool hier, const DfnFrame* frame, const int32_t* p
     A.ranks = ranks;
     A.zero_buf = zero_buf;
     A.zero_floats = zero_buf ? zero_floats : 0;
+    if (rin) {
+        A.rays = rin->rays;
+        A.bounds = rin->bounds;
+        return launched(launch_composite_bwd_rays(A, hier, (hipStream_t)stream), hier ? "composite_bwd_hier_kernel(rays)" : "composite_bwd_kernel(rays)");
+    }
     if (hier) return launched(launch_composite_bwd_hier(A, (hipStream_t)stream), "composite_bwd_hier_kernel");
     return launched(launch_composite_bwd(A, (hipStream_t)stream), "composite_bwd_kernel");
 }
@@ -795,6 +850,22 @@ int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, co
         return fail(DFN_E_ARG, "dfn_composite_bwd_hier_z: zero_buf must be 16-byte aligned");
     return composite_bwd_impl(true, frame, pix_index, bg_f32, bg_u8, samples, z_all, ranks, d_rgb_head, d_rgb_com, dsamples, zero_buf,
                               zero_floats, stream);
+}
+
+int dfn_composite_bwd_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                             const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                             long zero_floats, void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return composite_bwd_impl(false, frame, nullptr, bg_f32, bg_u8, samples, nullptr, nullptr, d_rgb_head, d_rgb_com, dsamples, zero_buf,
+                              zero_floats, stream, &rin);
+}
+int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                  const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                  const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                  void* stream) {
+    const RaysIn rin = {rays, bounds};
+    return composite_bwd_impl(true, frame, nullptr, bg_f32, bg_u8, samples, z_all, ranks, d_rgb_head, d_rgb_com, dsamples, zero_buf,
+                              zero_floats, stream, &rin);
 }
 
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,

@@ -22,7 +22,10 @@ struct RenderArgs {
     // the optional per-sample outputs - or, in an aux launch (`aux` below; the two are never combined, and the aux kernels write no
     // per-sample output), the per-ray aux outputs in the same slots: the argument block, hence the kernel argument segment of every
     // kernel, keeps its size and offsets
-    union { float* w_head; float* aux_head; unsigned char* alpha8_head; };      // aux: f32 [ray_count,2] {acc, depth}; u8 route: [ray_count]
+    // (training launch on caller-supplied rays, `use_rays` == 2: the recorder needs samples_out, so the per-ray `train_bounds` - optional
+    // f32 [ray_count,2] = (near, far), NULL = frame.z_near / z_far - ride in the w_head slot, which every training launch leaves null;
+    // those kernels write no per-sample weights of the head image)
+    union { float* w_head; float* aux_head; unsigned char* alpha8_head; const float* train_bounds; };      // aux: f32 [ray_count,2] {acc, depth}; u8 route: [ray_count]
     union { float* w_com; float* aux_com; unsigned char* alpha8_com; };
     union { float* z_out; unsigned short* depth16_head; };                      // aux, u8 route: [ray_count]
     int out_u8;                 // rgb_head / rgb_com point at uint8 [ray_count,3]: to8b in the epilogue (HELP:17)
@@ -39,7 +42,9 @@ struct RenderArgs {
     unsigned* masks[2];
     long NP;
     int act_e4m3;               // 16-bit training forward: act_T as MX-fp8 e4m3 instead of MX-fp4 (DFN_TRAIN_ACT_E4M3)
-    int use_rays;               // 1: launch the rays instantiation (render_kernel<TW | TIER_RAYS>; inference only) - host-side dispatch only
+    int use_rays;               // 1: launch the rays instantiation (render_kernel<TW | TIER_RAYS>; inference) - host-side dispatch only
+                                // 2: the TRAINING forward on caller-supplied rays (render_kernel<TIER | TIER_RAYS, true, TRAIN>: recorder
+                                // on, `train_bounds` above, no loss epilogue - its targets are gathered by pixel id)
                                 // (sits in the padding in front of `loss`: the argument block keeps its size and offsets)
     // training forward with the loss in its epilogue (dfn_train_fwd_loss; losses == null: off)
     DfnTrainLoss loss;

@@ -14,19 +14,20 @@ namespace dfn {
     X(T, TIER_ZVALS) X(T, TIER_W128 | TIER_ZVALS)
 #define DFN_RENDER_VARIANTS(X) \
     DFN_INFERENCE_VARIANTS(X, TIER_F32) DFN_INFERENCE_VARIANTS(X, TIER_F16) DFN_INFERENCE_VARIANTS(X, TIER_F16X3) \
-    X(TIER_BF16, 0) X(TIER_BF16, TIER_E4M3)
+    X(TIER_BF16, 0) X(TIER_BF16, TIER_E4M3) \
+    X(TIER_F32, TIER_RAYS | TIER_TRAIN) X(TIER_BF16, TIER_RAYS | TIER_TRAIN) X(TIER_BF16, TIER_RAYS | TIER_TRAIN | TIER_E4M3)
 
 struct Variant {
     hipError_t (*render)(const RenderArgs&, hipStream_t);
     hipError_t (*decoder)(const DecoderArgs&, hipStream_t);
 };
-enum Mode { MODE_PLAIN, MODE_AUX, MODE_RAYS, MODE_E4M3, MODE_ZVALS, N_MODES };
+enum Mode { MODE_PLAIN, MODE_AUX, MODE_RAYS, MODE_E4M3, MODE_ZVALS, MODE_RAYS_TRAIN, MODE_RAYS_TRAIN_E4M3, N_MODES };
 constexpr int N_TIERS = TIER_F16X3 + 1;
 struct VariantTable { Variant at[N_TIERS][2][N_MODES]; };         // [tier][width == 128][mode]; no such variant: null
 static constexpr VariantTable make_table() {
     VariantTable t{};
 #define X(T, F) \
-    t.at[T][((F) & TIER_W128) != 0][(F) & TIER_RAYS ? MODE_RAYS : (F) & TIER_ZVALS ? MODE_ZVALS : (F) & TIER_AUX ? MODE_AUX : (F) & TIER_E4M3 ? MODE_E4M3 : MODE_PLAIN] = \
+    t.at[T][((F) & TIER_W128) != 0][(F) & TIER_TRAIN ? ((F) & TIER_E4M3 ? MODE_RAYS_TRAIN_E4M3 : MODE_RAYS_TRAIN) : (F) & TIER_RAYS ? MODE_RAYS : (F) & TIER_ZVALS ? MODE_ZVALS : (F) & TIER_AUX ? MODE_AUX : (F) & TIER_E4M3 ? MODE_E4M3 : MODE_PLAIN] = \
         {launch_render_tier<T, (F)>, launch_decoder_tier<T, (F)>};
     DFN_RENDER_VARIANTS(X)
 #undef X
@@ -42,8 +43,9 @@ hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int widt
     // rays first: a rays launch carries `bounds` in the recorder's samples_out slot (bf16: refused by the API); then aux (bf16 has no
     // aux kernels; the API refuses it before); then the width (bf16: the training tier stays padded; the API refuses it before).
     // The 16-bit training step with the e4m3 opt-out for act_T: those two kernels are a variant of their own.  A z launch: `zvals` shares
-    // the argument slot of the recorder's ranks_out and of the aux route's depth16_com - it is one when neither of those is on
-    const int mode = A.use_rays ? MODE_RAYS : A.aux ? MODE_AUX : (!A.samples_out && A.zvals) ? MODE_ZVALS : (tier == TIER_BF16 && A.samples_out && A.act_e4m3) ? MODE_E4M3 : MODE_PLAIN;
+    // the argument slot of the recorder's ranks_out and of the aux route's depth16_com - it is one when neither of those is on.
+    // use_rays == 2: the training forward on caller-supplied rays (recorder on, bounds in the w_head slot): variants of their own
+    const int mode = A.use_rays == 2 ? (tier == TIER_BF16 && A.act_e4m3 ? MODE_RAYS_TRAIN_E4M3 : MODE_RAYS_TRAIN) : A.use_rays ? MODE_RAYS : A.aux ? MODE_AUX : (!A.samples_out && A.zvals) ? MODE_ZVALS : (tier == TIER_BF16 && A.samples_out && A.act_e4m3) ? MODE_E4M3 : MODE_PLAIN;
     const Variant* v = variant(tier, width, mode);
     return v && v->render ? v->render(A, st) : hipErrorInvalidValue;
 }

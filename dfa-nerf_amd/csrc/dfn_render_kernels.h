@@ -160,6 +160,10 @@ template <int TIER, bool TWO = false> struct KernelLds {
 // depths, in place of F.z_near / F.z_far.  The background is indexed by the ray (bg[r]); there is no pixel id.  Only the "this
 // wave's ray" block differs: the ray still lives in the LDS state, so nothing new is live across an MLP pass, and everything
 // after that block - coarse loop, sampler, merge, fine passes, compositing, per-sample outputs, epilogues - is the same code.
+// TIER_RAYS with TRAIN != 0 (two fields, padded width; f32 and bf16, ACT4 both ways): the training forwards on caller-supplied rays
+// (include/dfanerf.h, dfn_train_rays_fwd / _hier).  The same "this wave's ray" block; the recorder owns samples_out, so the bounds are
+// read from the w_head slot (A.train_bounds, dfn_params.h), the head weights are not written, and the loss epilogue - which gathers
+// its targets by pixel id - is compiled out.
 // TIER_ZVALS in TW (inference only, never with TIER_AUX or TIER_RAYS): the wave's sample depths are read from memory instead of being
 // spaced between near and far (include/dfanerf.h, dfn_render_z_fwd).  Row r of A.zvals is the NC non-decreasing depths of the launch's
 // ray r - the row index of the outputs, not the pixel id.  The launch is coarse-only (n_fine == 0) with NC = 32 ... 192 in steps of 32:
@@ -175,7 +179,10 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     constexpr bool AUX = (TW & TIER_AUX) != 0;
     static_assert(!AUX || TRAIN == 0, "the aux outputs are inference only");
     constexpr bool RAYS = (TW & TIER_RAYS) != 0;
-    static_assert(!RAYS || TRAIN == 0, "caller-supplied rays are inference only");
+    // the training forward on caller-supplied rays (dfn_train_rays_fwd / _hier): the recorder owns samples_out, so the per-ray
+    // bounds come through the w_head slot (dfn_params.h: train_bounds) and the kernel writes no head weights; no loss epilogue
+    constexpr bool RAYS_TRAIN = RAYS && TRAIN != 0;
+    static_assert(!RAYS_TRAIN || (TWO && HT == 8), "the training step renders two fields at the padded width");
     static_assert(!RAYS || !AUX, "no aux form for caller-supplied rays");
     constexpr bool ZVALS = (TW & TIER_ZVALS) != 0;
     static_assert(!ZVALS || TRAIN == 0, "caller-supplied depths are inference only");
@@ -289,7 +296,12 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
                 ot[k] = TWO ? row[6 + k] : oh[k];
                 dt[k] = TWO ? row[9 + k] : dh[k];
             }
-            if (A.bounds) {                          // (uniform over the launch)
+            if constexpr (RAYS_TRAIN) {
+                if (A.train_bounds) {               // (uniform over the launch)
+                    z_near = A.train_bounds[(size_t)r * 2];
+                    z_far = A.train_bounds[(size_t)r * 2 + 1];
+                }
+            } else if (A.bounds) {                   // (uniform over the launch)
                 z_near = A.bounds[(size_t)r * 2];
                 z_far = A.bounds[(size_t)r * 2 + 1];
             }
@@ -491,7 +503,9 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
                     if (A.w_com && two) *(float*)((char*)A.w_com + off) = w_c;
                     if (A.z_out) *(float*)((char*)A.z_out + off) = z;
                 } else {
-                    if (A.w_head) A.w_head[(size_t)r_raw * NC + si] = w_h;
+                    if constexpr (!RAYS_TRAIN) {     // (the slot holds train_bounds there)
+                        if (A.w_head) A.w_head[(size_t)r_raw * NC + si] = w_h;
+                    }
                     if (A.w_com && two) A.w_com[(size_t)r_raw * NC + si] = w_c;
                     if (A.z_out) A.z_out[(size_t)r_raw * NC + si] = z;
                 }
@@ -646,7 +660,8 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             }
             if (++tile < KF) continue;
             wave_lds_fence();
-            composite_merged(true, A.w_head);
+            if constexpr (RAYS_TRAIN) composite_merged(true, nullptr);      // (the slot holds train_bounds there)
+            else composite_merged(true, A.w_head);
             if (!two) break;
             phase = PH_FINE_T;
             tile = 0;
@@ -729,7 +744,7 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
             }
         }
     }
-    if constexpr (TRAIN != 0) {
+    if constexpr (TRAIN != 0 && !RAYS) {     // (a rays launch has no pixel id to gather targets by: no _loss form)
         // dfn_train_fwd_loss: the step's loss and d loss / d rgb from the epilogue (include/dfanerf.h).  Ray: its target pixel,
         // its row of d_rgb, its squared error; workgroup: its rays' in ray order; the last workgroup to get here (ticket in
         // the caller's workspace): the workgroups' in workgroup order.
@@ -890,7 +905,7 @@ template <typename K> static hipError_t set_lds(K kernel, int lds) {
     return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 template <int TIER, bool TWO, int TRAIN = 0, bool ACT4 = true, int W128 = 0> static hipError_t launch_render_t(const RenderArgs& A, hipStream_t st) {
-    static_assert((W128 & ~(TIER_W128 | TIER_AUX | TIER_RAYS | TIER_ZVALS)) == 0 && (W128 == 0 || TRAIN == 0), "widths / aux / rays / zvals: inference only");      // (W128 also carries TIER_AUX / TIER_RAYS / TIER_ZVALS)
+    static_assert((W128 & ~(TIER_W128 | TIER_AUX | TIER_RAYS | TIER_ZVALS)) == 0 && (W128 == 0 || TRAIN == 0 || W128 == TIER_RAYS), "widths / aux / zvals: inference only");      // (W128 also carries TIER_AUX / TIER_RAYS / TIER_ZVALS)
     using C = TierCfg<TIER>;
     const int lds = KernelLds<TIER, TWO>::TOTAL;
     static bool attr_done = false;
@@ -926,12 +941,20 @@ template <int TIER, bool TORSO, bool REC = false, int W128 = 0> static hipError_
 // TIER_ZVALS (dfn_render_z_fwd / dfn_render_z_fwd_u8; the recorder's ranks_out slot carries `zvals`), the last three with or without
 // TIER_W128.  TIER_E4M3: the two 16-bit training forwards whose recorder writes act_T as MX-fp8 e4m3
 // (the run-time opt-out of the narrow activation format, for A/B runs of the two formats on real data in one process), nothing else.
+// TIER_RAYS | TIER_TRAIN [| TIER_E4M3]: the two training forwards on caller-supplied rays (dfn_train_rays_fwd / _hier: RenderArgs.use_rays
+// == 2, recorder on), in a trainable tier; with TIER_E4M3 (bf16) the ones whose recorder writes e4m3.  Nothing else.
 template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st) {
-    if constexpr (FLAGS == TIER_E4M3) {
+    if constexpr ((FLAGS & TIER_TRAIN) != 0) {
+        static_assert((FLAGS & ~TIER_E4M3) == (TIER_RAYS | TIER_TRAIN) && tier_trainable(TIER), "TIER_TRAIN: the rays training forwards");
+        static_assert((FLAGS & TIER_E4M3) == 0 || TIER == TIER_BF16, "the e4m3 recorder is the bf16 tier's");
+        constexpr bool ACT4 = (FLAGS & TIER_E4M3) == 0;
+        if (A.use_rays != 2 || !A.rays || !A.samples_out || A.aux || A.frame.fields != 2 || A.loss.losses) return hipErrorInvalidValue;
+        return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2, ACT4, TIER_RAYS>(A, st) : launch_render_t<TIER, true, 1, ACT4, TIER_RAYS>(A, st);
+    } else if constexpr (FLAGS == TIER_E4M3) {
         return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2, false>(A, st) : launch_render_t<TIER, true, 1, false>(A, st);
     } else {
         if constexpr ((FLAGS & TIER_RAYS) != 0) {
-            if (!A.use_rays || A.aux || !A.rays) return hipErrorInvalidValue;
+            if (A.use_rays != 1 || A.aux || !A.rays) return hipErrorInvalidValue;
         } else if constexpr ((FLAGS & TIER_ZVALS) != 0) {
             if (A.samples_out || A.aux || A.use_rays || !A.zvals || A.frame.n_fine != 0) return hipErrorInvalidValue;
         } else if constexpr ((FLAGS & TIER_AUX) != 0) {

@@ -16,7 +16,9 @@
 //   [TIER_W128 |] TIER_RAYS  the render kernels for caller-supplied rays (RenderArgs.use_rays): render only
 //   [TIER_W128 |] TIER_ZVALS the render kernels for caller-supplied sample depths (RenderArgs.zvals; coarse-only, 32 ... 192 samples): render only
 //   TIER_E4M3              bf16 only: the two training forwards whose recorder writes act_T as MX-fp8 e4m3
-// The flagged variants exist for the inference tiers (f32, f16, f16x3); bf16 is the training tier.
+//   TIER_RAYS | TIER_TRAIN [| TIER_E4M3]   f32 and bf16: the two training forwards on caller-supplied rays (RenderArgs.use_rays == 2:
+//                          render_kernel<TIER | TIER_RAYS, true, TRAIN = 1, 2>); with TIER_E4M3 (bf16) the e4m3 recorder's.  Nothing else
+// The other flagged variants exist for the inference tiers (f32, f16, f16x3); bf16 is the training tier.
 //
 // The library's own list of variants is the dispatch table of dfn_render.hip, which names each variant's two launchers by
 // <tier, flags>.  The two lists cannot disagree silently: an entry of the table without an object of exactly that tier and

@@ -34,12 +34,21 @@ struct CompositeBwdArgs {
     float* zero_buf;
     long zero_floats;
 };
+// the step on caller-supplied rays (dfn_composite_bwd_rays_z / _hier_rays_z: the <.., RAYS> kernels) gains what the forward read: rays
+// f32 [rays][12] = o_head, d_head, o_torso, d_torso (the ray norms come from the directions), bounds f32 [rays][2] = (near, far) or null
+// = frame.z_near / z_far (the coarse-only kernel's depths).  No pixel id (pix_index is not read): bg row r is ray r's.  A block of its
+// own behind the plain one, so that the plain kernels' argument segment - and with it their ISA - stays what it was
+struct CompositeBwdRaysArgs : CompositeBwdArgs {
+    const float* rays;
+    const float* bounds;
+};
 
 hipError_t launch_mlp_bwd(int tier, int field, const MlpBwdArgs& A, hipStream_t st);
 hipError_t launch_mlp_bwd_bf16(bool torso, const MlpBwdArgs& A, hipStream_t st);     // dfn_bwd_bf16.hip
 void bwd_program_info(int tier, int field, ProgramInfo* out);
 hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st);
 hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st);      // n_fine in {64, 128}
+hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st);      // fields == 2; counts as the two above
 // Split-K partials: C [ksplit][c_stride] and dbias [ksplit][n_bias], one writer per element and slice (no atomics);
 // launch_reduce_scatter / launch_reduce_bias add the slices in index order (bit-reproducible gradients).
 // f32 tier: wgrad_full_kernel + wgrad_narrow_kernel (dfn_plan.h: WNItem)

@@ -60,6 +60,19 @@ __device__ __forceinline__ void composite_zero_fill(const CompositeBwdArgs& A) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (blockIdx.x == 0 && threadIdx.x < (A.zero_floats & 3)) A.zero_buf[(n4 << 2) + threadIdx.x] = 0.f;
 }
+// the argument block of the compositing backward kernels: the plain block, or the rays form's longer one (dfn_train.h)
+template <bool RAYS> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
+template <> struct CompositeArgsOf<true> { typedef CompositeBwdRaysArgs type; };
+// RAYS kernels (dfn_composite_bwd_rays_z / _hier_rays_z): the norms of the two directions of row `ray` of A.rays (o_head, d_head,
+// o_torso, d_torso), in the arithmetic of the forward's norm3 (dfn_render_kernels.h)
+__device__ __forceinline__ void ray_row_norms(const float* rays, long ray, float (&nrm)[2]) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const float* d = rays + ray * 12 + 6 * b + 3;
+        const float d0 = d[0], d1 = d[1], d2 = d[2];
+        nrm[b] = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    }
+}
 // KL consecutive samples per lane (KL = 1: --N_samples 32 / 64, lanes beyond the ray's samples idle; KL = 2: 128), round 6.
 // Sample i = lane KL + k.  The scans run over the lanes' local products / sums and are carried across a lane's KL positions;
 // with KL = 1 and 64 samples the arithmetic is the round 1-5 kernel's.
@@ -93,36 +106,47 @@ __device__ __forceinline__ void weights_bwd_n(const float (&sigma)[KL], const fl
         suf += wq[k];
     }
 }
-template <int KL>
-__global__ void composite_bwd_kernel(const CompositeBwdArgs A) {
+// RAYS: the step on caller-supplied rays - the norms from the directions of row `ray`, the depths between that ray's (near, far) when
+// bounds are given, the background of the last sample from row `ray`; everything behind the geometry is the same code
+template <int KL, bool RAYS = false>
+__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS>::type A) {
     composite_zero_fill(A);
     const int lane = threadIdx.x & 63;
     const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= A.frame.ray_count) return;
     const DfnFrame& F = A.frame;
     const int NC = F.n_coarse;
-    const int pix = A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
-    // geometry (same arithmetic as the forward)
-    const int y = pix / F.W, x = pix - y * F.W;
-    const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
+    // (RAYS: the background row of a supplied ray is the ray's own)
+    const int pix = RAYS ? (int)ray : A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
     float nrm[2];
+    float nf[2] = {0.f, 0.f};                        // RAYS: this ray's (near, far)
+    if constexpr (RAYS) {
+        ray_row_norms(A.rays, ray, nrm);
+        nf[0] = A.bounds ? A.bounds[ray * 2] : F.z_near;             // (uniform over the launch)
+        nf[1] = A.bounds ? A.bounds[ray * 2 + 1] : F.z_far;
+    } else {
+        // geometry (same arithmetic as the forward)
+        const int y = pix / F.W, x = pix - y * F.W;
+        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const float* P = b ? F.pose_body : F.pose;
-        float acc = 0.f;
+        for (int b = 0; b < 2; ++b) {
+            const float* P = b ? F.pose_body : F.pose;
+            float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
-                                      __fmul_rn(-1.0f, P[4 * k + 2]));
-            acc = __fadd_rn(acc, __fmul_rn(d, d));
+            for (int k = 0; k < 3; ++k) {
+                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
+                                          __fmul_rn(-1.0f, P[4 * k + 2]));
+                acc = __fadd_rn(acc, __fmul_rn(d, d));
+            }
+            nrm[b] = sqrtf(acc);
         }
-        nrm[b] = sqrtf(acc);
     }
     const float step = __fdiv_rn(1.0f, (float)(NC - 1));
     auto tval = [&](int i) { return (i < NC / 2) ? __fmul_rn(step, (float)i) : fmaf(-step, (float)(NC - 1 - i), 1.0f); };
     auto zval = [&](int i) {
         const float t = tval(i);
-        return __fadd_rn(__fmul_rn(F.z_near, __fsub_rn(1.0f, t)), __fmul_rn(F.z_far, t));
+        if constexpr (RAYS) return __fadd_rn(__fmul_rn(nf[0], __fsub_rn(1.0f, t)), __fmul_rn(nf[1], t));
+        else return __fadd_rn(__fmul_rn(F.z_near, __fsub_rn(1.0f, t)), __fmul_rn(F.z_far, t));
     };
     const bool cbg = F.concate_bg != 0;
     bool live[KL], last[KL], h_is_bg[KL];
@@ -251,8 +275,9 @@ hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st) {
 // then the fine ones: the order of the recorded activations, which is what the dX chain walks), its merged rank, and the
 // merged depths; the fine depths are constants (no gradient through sample_pdf), so this is the same differentiation as
 // composite_bwd_kernel with run-time depths and the scans carried across a lane's K positions.
-template <int K>
-__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const CompositeBwdArgs A) {
+// RAYS: as in composite_bwd_kernel - the norms and the background row only (the depths are z_all's)
+template <int K, bool RAYS = false>
+__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS>::type A) {
     constexpr int S = 64 * K;
     __shared__ unsigned char inv_s[4][S];
     composite_zero_fill(A);
@@ -260,21 +285,25 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const Composite
     const long ray = (long)blockIdx.x * 4 + wv;
     if (ray >= A.frame.ray_count) return;
     const DfnFrame& F = A.frame;
-    const int pix = A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
-    const int y = pix / F.W, x = pix - y * F.W;
-    const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
+    const int pix = RAYS ? (int)ray : A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
     float nrm[2];
+    if constexpr (RAYS) {
+        ray_row_norms(A.rays, ray, nrm);
+    } else {
+        const int y = pix / F.W, x = pix - y * F.W;
+        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const float* P = b ? F.pose_body : F.pose;
-        float acc = 0.f;
+        for (int b = 0; b < 2; ++b) {
+            const float* P = b ? F.pose_body : F.pose;
+            float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
-                                      __fmul_rn(-1.0f, P[4 * k + 2]));
-            acc = __fadd_rn(acc, __fmul_rn(d, d));
+            for (int k = 0; k < 3; ++k) {
+                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
+                                          __fmul_rn(-1.0f, P[4 * k + 2]));
+                acc = __fadd_rn(acc, __fmul_rn(d, d));
+            }
+            nrm[b] = sqrtf(acc);
         }
-        nrm[b] = sqrtf(acc);
     }
     // inverse of the rank map: merged position -> evaluation index
     unsigned char* inv = inv_s[wv];
@@ -414,6 +443,22 @@ hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st) 
     if (K == 2) hipLaunchKernelGGL(composite_bwd_hier_kernel<2>, dim3(blocks), dim3(256), 0, st, A);
     else if (K == 3) hipLaunchKernelGGL(composite_bwd_hier_kernel<3>, dim3(blocks), dim3(256), 0, st, A);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// the two launches above on caller-supplied rays (a rays row holds both fields' rays: two fields only)
+hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st) {
+    const int blocks = (A.frame.ray_count + 3) / 4;
+    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
+    if (!A.rays || A.frame.fields != 2) return hipErrorInvalidValue;
+    if (hier) {
+        if (nc != 64 || (A.frame.n_fine != 64 && A.frame.n_fine != 128)) return hipErrorInvalidValue;
+        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, true>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, true>), dim3(blocks), dim3(256), 0, st, A);
+    } else {
+        if ((nc != 128 && nc != 64 && nc != 32) || A.frame.n_fine != 0) return hipErrorInvalidValue;
+        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, true>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_bwd_kernel<1, true>), dim3(blocks), dim3(256), 0, st, A);
+    }
     return hipGetLastError();
 }
 

@@ -98,6 +98,12 @@ def _load():
         "dfn_train_prepare": (i32, [i32, fp, fp, fp, fp, fp, vp, vp, vp, vp, fp, fp, vp]),
         "dfn_train_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, vp, vp, vp, vp, vp]),
         "dfn_train_fwd_hier": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, vp, vp, vp, vp, fp, vp, vp]),
+        # the training step on caller-supplied rays: (rays, bounds) in place of pix_index
+        "dfn_train_rays_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, fp, fp, fp, vp, vp, vp, vp, vp]),
+        "dfn_train_rays_fwd_hier": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, fp, fp, vp, fp, fp, fp, vp, vp, vp, vp, fp, vp,
+                                          vp]),
+        "dfn_composite_bwd_rays_z": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, lg, vp]),
+        "dfn_composite_bwd_hier_rays_z": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, vp, fp, fp, fp, fp, lg, vp]),
         "dfn_train_loss_floats": (lg, [i32]),
         "dfn_train_fwd_loss": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, vp, vp, vp, vp,
                                      C.POINTER(DfnTrainLoss), vp]),

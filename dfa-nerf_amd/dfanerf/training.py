@@ -201,7 +201,21 @@ class FusedTrainFn(torch.autograd.Function):
         return _fused_backward(ctx, d_h, d_c)
 
 
-def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None):
+class FusedTrainRaysFn(torch.autograd.Function):
+    """FusedTrainFn on caller-supplied rays [n,12] (o_head, d_head, o_torso, d_torso) with optional per-ray bounds [n,2]:
+    dfn_train_rays_fwd[_hier] and dfn_composite_bwd[_hier]_rays_z in place of the pixel-id calls; everything else is the same step."""
+
+    @staticmethod
+    def forward(ctx, sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, defer=None):
+        return _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, None, z_shape, z_app, defer, rays=rays, bounds=bounds)
+
+    @staticmethod
+    def backward(ctx, d_h, d_c):
+        return _fused_backward(ctx, d_h, d_c) + (None,)       # (one input more than FusedTrainFn: rays, bounds for pix_index)
+
+
+def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None, rays=None, bounds=None):
+    # rays / bounds: the step on caller-supplied rays (FusedTrainRaysFn; no pixel ids, no loss epilogue)
     # loss: a _lib.DfnTrainLoss -> the forward's epilogue forms the step's loss and d loss / d rgb (dfn_train_fwd*_loss)
     # defer: the SignalTrainer whose _SignalFn produced both signals (their backward then picks d(signal) up on its own
     # streams and the main stream never waits for it), or None
@@ -223,7 +237,17 @@ def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape,
     rgb_c = torch.empty(n, 3, dtype=torch.float32, device=dev)
     bg_f32 = bg if bg.dtype == torch.float32 else None
     bg_u8 = bg if bg.dtype == torch.uint8 else None
-    if loss is not None and buf.n_fine:
+    if rays is not None and buf.n_fine:
+        check(lib.dfn_train_rays_fwd_hier(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
+                                          _ptr(rays), _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c),
+                                          _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
+                                          _ptr(buf.masks[1]), _ptr(buf.z_all), _ptr(buf.ranks), st), "dfn_train_rays_fwd_hier")
+    elif rays is not None:
+        check(lib.dfn_train_rays_fwd(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
+                                     _ptr(rays), _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c),
+                                     _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
+                                     _ptr(buf.masks[1]), st), "dfn_train_rays_fwd")
+    elif loss is not None and buf.n_fine:
         check(lib.dfn_train_fwd_hier_loss(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
                                           _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c),
                                           _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
@@ -245,6 +269,7 @@ def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape,
                                 _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
                                 _ptr(buf.masks[1]), st), "dfn_train_fwd")
     ctx.buf, ctx.frame, ctx.bg, ctx.pix = buf, frame, bg, pix_index
+    ctx.rays, ctx.bounds = rays, bounds
     # the recorded arrays (and FusedTrainLossFn's d loss / d rgb) live in `buf` and are overwritten by the next forward
     # through it: a backward is only valid for the LAST forward (no gradient accumulation over micro-batches through one
     # TrainBuffers, no retain_graph across forwards) - stamped here, checked in _fused_backward
@@ -277,7 +302,15 @@ def _fused_backward(ctx, d_h, d_c):
     if not reuse:
         g_flat = _grad_buffer(buf.net, "_g_flat", flat, buf.params)
     zb, zn = (_ptr(g_flat), g_flat.numel()) if reuse else (None, 0)
-    if buf.n_fine:
+    if ctx.rays is not None and buf.n_fine:
+        check(lib.dfn_composite_bwd_hier_rays_z(C.byref(frame), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(bg_f32), _ptr(bg_u8),
+                                                _ptr(buf.samples), _ptr(buf.z_all), _ptr(buf.ranks), _ptr(d_h), _ptr(d_c),
+                                                _ptr(buf.dsamples), zb, zn, st), "dfn_composite_bwd_hier_rays_z")
+    elif ctx.rays is not None:
+        check(lib.dfn_composite_bwd_rays_z(C.byref(frame), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(bg_f32), _ptr(bg_u8),
+                                           _ptr(buf.samples), _ptr(d_h), _ptr(d_c), _ptr(buf.dsamples), zb, zn, st),
+              "dfn_composite_bwd_rays_z")
+    elif buf.n_fine:
         check(lib.dfn_composite_bwd_hier_z(C.byref(frame), _ptr(ctx.pix), _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples),
                                            _ptr(buf.z_all), _ptr(buf.ranks), _ptr(d_h), _ptr(d_c), _ptr(buf.dsamples), zb, zn,
                                            st), "dfn_composite_bwd_hier_z")
@@ -772,13 +805,44 @@ class _SignalFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
-def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, signal_trainer=None):
+def _check_rays(buf, bg, pix_index, rays, bounds):
+    """render_train(rays=...): every argument of the rays form, refused by name before any launch"""
+    n, dev = buf.n_rays, buf.samples.device
+    if pix_index is not None:
+        raise ValueError("render_train: pix_index must be None when rays are given (a supplied ray has no pixel id; bg row r is "
+                         "the background of ray r)")
+    if not (torch.is_tensor(rays) and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 12 and
+            rays.shape[0] == n and rays.is_contiguous() and rays.device == dev):
+        raise ValueError(f"render_train: rays must be a contiguous float32 [{n}, 12] tensor on {dev} (o_head, d_head, o_torso, d_torso: "
+                         f"engine.pack_rays), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}"
+                         f"{' ' + str(rays.dtype) + ' on ' + str(rays.device) if torch.is_tensor(rays) else ''}")
+    if not (torch.is_tensor(bg) and bg.dtype in (torch.float32, torch.uint8) and bg.dim() == 2 and tuple(bg.shape) == (n, 3) and
+            bg.is_contiguous() and bg.device == dev):
+        raise ValueError(f"render_train: with rays, bg must be a contiguous float32 / uint8 [{n}, 3] tensor on {dev} (row r = the "
+                         f"background of ray r), got {tuple(bg.shape) if torch.is_tensor(bg) else type(bg).__name__}")
+    if bounds is not None and not (torch.is_tensor(bounds) and bounds.dtype == torch.float32 and tuple(bounds.shape) == (n, 2) and
+                                   bounds.is_contiguous() and bounds.device == dev):
+        raise ValueError(f"render_train: bounds must be None or a contiguous float32 [{n}, 2] tensor on {dev} ((near, far) per ray), got "
+                         f"{tuple(bounds.shape) if torch.is_tensor(bounds) else type(bounds).__name__}")
+
+
+def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, signal_trainer=None, rays=None, bounds=None):
     """Differentiable (w.r.t. the decoder parameters and the two signals) two-field render of the
     pixels `pix_index` [n] (int32, y*W+x): coarse (frame.n_fine == 0, the reference's step) or hierarchical (64 / 128
     fine samples at detached depths; buf = TrainBuffers(..., n_fine=...)).  Returns rgb_head, rgb_com [n,3].  Fold and its backward run in HIP, the
     decoder gradients are deposited into .grad by the backward (FusedTrainFn).  One forward per backward: the recorded
     activations live in `buf` and the next forward overwrites them.  signal_trainer: the SignalTrainer whose encode()
-    produced BOTH signals for this call (None otherwise): d(signal) then stays on its streams (FusedTrainFn.backward)."""
+    produced BOTH signals for this call (None otherwise): d(signal) then stays on its streams (FusedTrainFn.backward).
+    rays (with pix_index None): train on caller-supplied rays instead of the frame's pinhole rays - float32 [n,12] on the device,
+    contiguous (o_head, d_head, o_torso, d_torso: engine.pack_rays; directions of any length), bg [n,3] = the background of ray r,
+    bounds None or float32 [n,2] = (near, far) per ray; the frame's poses, intrinsics, H, W are ignored (FusedTrainRaysFn).  Anything
+    else is a ValueError naming the argument, before any launch."""
+    if rays is not None or bounds is not None:
+        if rays is None:
+            raise ValueError("render_train: bounds are the per-ray (near, far) of caller-supplied rays: rays is None")
+        if frame.ray_count != buf.n_rays:
+            raise ValueError(f"render_train: the buffers were sized for {buf.n_rays} rays, the frame has {frame.ray_count}")
+        _check_rays(buf, bg, pix_index, rays, bounds)
     if frame.ray_count != buf.n_rays or (pix_index is not None and pix_index.numel() != buf.n_rays):
         raise ValueError(f"render_train: the buffers were sized for {buf.n_rays} rays, the frame has {frame.ray_count}"
                          f" (pix_index {None if pix_index is None else pix_index.numel()})")
@@ -794,13 +858,17 @@ def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z
         node = sig_head.grad_fn
         if node is None or node is not sig_torso.grad_fn or type(node).__name__ != "_SignalFnBackward":
             signal_trainer = None
+    if rays is not None:
+        return FusedTrainRaysFn.apply(sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, signal_trainer)
     return FusedTrainFn.apply(sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, signal_trainer)
 
 
 def render_train_loss(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, img_head, img_com,
                       signal_trainer=None):
     """render_train + the step's loss against uint8 ground-truth frames [H*W,3] resident on the device, as one autograd node
-    (FusedTrainLossFn): -> loss (= loss_com + loss_head), loss_head, loss_com, rgb_head, rgb_com."""
+    (FusedTrainLossFn): -> loss (= loss_com + loss_head), loss_head, loss_com, rgb_head, rgb_com.
+    There is no rays form of this call: the forward's loss epilogue gathers its targets by pixel id.  A step on caller-supplied
+    rays is render_train(rays=...) with the loss formed on rgb_head / rgb_com by the caller (the two-node route of --use_L1)."""
     if frame.ray_count != buf.n_rays or pix_index is None or pix_index.numel() != buf.n_rays:
         raise ValueError(f"render_train_loss: the buffers were sized for {buf.n_rays} rays, the frame has {frame.ray_count}")
     if frame.n_fine != buf.n_fine or frame.n_coarse != buf.n_coarse or frame.fields != 2:

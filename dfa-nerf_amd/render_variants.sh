@@ -29,6 +29,9 @@ f16x3_z         TIER_F16X3  TIER_ZVALS
 f32_w128_z      TIER_F32    TIER_W128|TIER_ZVALS
 f16_w128_z      TIER_F16    TIER_W128|TIER_ZVALS
 f16x3_w128_z    TIER_F16X3  TIER_W128|TIER_ZVALS
+f32_rays_train  TIER_F32    TIER_RAYS|TIER_TRAIN
+bf16_rays_train TIER_BF16   TIER_RAYS|TIER_TRAIN
+bf16e_rays_train TIER_BF16  TIER_RAYS|TIER_TRAIN|TIER_E4M3
 "
 # variant_units [tier ...]: the unit names (dfn_render_<name>) of the variants of these tiers, or of all of them
 variant_units() {

@@ -70,7 +70,9 @@ const char* dfn_last_error(void);
  * expected depth next to the RGB; inference tiers, both widths; nothing else changes); + dfn_render_rays_fwd, dfn_render_rays_fwd_u8
  * (the fused renderer on caller-supplied rays; inference tiers, both widths; nothing else changes, the version string stays);
  * + dfn_render_z_fwd, dfn_render_z_fwd_u8 (the fused renderer at caller-supplied sample depths, 32 ... 192 per ray) and dfn_fine_depths
- * (the fused fine sampler + merge on its own); inference tiers, both widths; nothing else changes, the version string stays.  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * (the fused fine sampler + merge on its own); inference tiers, both widths; nothing else changes, the version string stays;
+ * + dfn_train_rays_fwd, dfn_train_rays_fwd_hier, dfn_composite_bwd_rays_z, dfn_composite_bwd_hier_rays_z (the fused training step on
+ * caller-supplied rays; f32 and bf16; nothing else changes, the version string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -233,8 +235,9 @@ int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_he
  * rays dfn_get_rays makes for a pose, bg rows gathered at the same pixels and no bounds (or bounds filled with z_near, z_far), every
  * output equals dfn_render_fwd's bit for bit: the kernels differ in where the ray comes from, nothing else.
  * Tiers DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3, with or without DFN_WIDTH_128.  DFN_E_ARG with a message, before any device
- * work: rays == NULL; DFN_TIER_BF16 (the training tier).  There is NO aux form (opacity / depth) and NO training form of these
- * entry points. */
+ * work: rays == NULL; DFN_TIER_BF16 (the training tier).  There is NO aux form (opacity / depth), and NO training form of THESE two
+ * entry points: they record nothing.  Training on caller-supplied rays is dfn_train_rays_fwd / dfn_train_rays_fwd_hier with
+ * dfn_composite_bwd_rays_z / dfn_composite_bwd_hier_rays_z, in the training section below (f32 and bf16). */
 int dfn_render_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                         const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
                         const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* weights_head,
@@ -399,6 +402,43 @@ int dfn_composite_bwd_z(const DfnFrame* frame, const int32_t* pix_index, const f
 int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                              const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
                              const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream);
+/* The training step on CALLER-SUPPLIED rays: dfn_train_fwd / dfn_train_fwd_hier and dfn_composite_bwd_z / dfn_composite_bwd_hier_z
+ * with the ray generation of the training loop (get_rays at the drawn pixels, HELP:449-465 with MAIN:829-841) and the launch-wide
+ * depth range (MAIN:612-619) replaced by data, as dfn_render_rays_fwd does for inference.  For training on rays jittered inside the
+ * pixel footprint, rays of several cameras in one batch, a lens model, or the NeRF lineage's per-ray near / far (ray_batch) - which
+ * otherwise means Decoder.forward under autograd on materialised [R * S, 3] points with the compositing in ATen.
+ *   rays    f32 [ray_count, 12], required: row r = o_head[3], d_head[3], o_torso[3], d_torso[3].  Directions of any length: sample
+ *           points o + d * z, distances multiplied by |d|, view direction d / |d| (DEC:337).
+ *   bounds  f32 [ray_count, 2] = (near, far) of ray r, optional: NULL = frame.z_near / frame.z_far for every ray.
+ *   bg_f32 / bg_u8  [ray_count, 3]: row r is the background of RAY r.  There is no pixel id.
+ * Frame fields used and IGNORED: dfn_render_rays_fwd's.  fields == 2 only (the training step renders both fields).
+ * Every other argument and buffer: the plain call's.  dfn_mlp_bwd, the weight-gradient calls, dfn_signal_grad and dfn_fold_bias_bwd
+ * read recorded arrays only and serve both forms.  The backward must be given the rays and bounds the forward read.
+ * Given the rays dfn_get_rays makes for the frame's two poses at the drawn pixels, bg rows gathered at the same pixels and no
+ * bounds (or bounds filled with z_near, z_far), every output of the four calls equals the plain call's bit for bit.
+ * There are NO _loss forms: the loss epilogue gathers its targets by pixel id.  The caller forms the loss on rgb_head / rgb_com.
+ * Tiers DFN_TIER_F32 / DFN_TIER_BF16 [| DFN_TRAIN_ACT_E4M3].  DFN_E_ARG with a message, before any device work: rays == NULL;
+ * DFN_TIER_F16 / DFN_TIER_F16X3 (inference only); DFN_WIDTH_128; fields != 2; sample counts the plain form refuses (forward:
+ * 32 / 64 / 128 coarse, or DfnFrame's pairs; backward: 32 / 64 / 128 coarse, or 64 + 64 | 128); DFN_TRAIN_ACT_E4M3 outside bf16. */
+int dfn_train_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                       const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                       const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples, void* act_head,
+                       uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, void* stream);
+int dfn_train_rays_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
+                            const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
+                            const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples,
+                            void* act_head, uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all,
+                            uint8_t* ranks, void* stream);
+/* ... and the compositing backward of that step (replaces autograd through MAIN:146-179, 706-709 on those rays): the ray norms from
+ * the directions of row r, the coarse depths between that ray's (near, far), the background of the last sample from row r.  zero_buf /
+ * zero_floats as in dfn_composite_bwd_z (NULL = none). */
+int dfn_composite_bwd_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                             const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                             long zero_floats, void* stream);
+int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                  const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                  const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                  void* stream);
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,
                 const uint32_t* masks, long NP, void* dy_T, void* stream);
 /* The weight-gradient plan of `field` (0 head, 1 torso), for tests and tools: what == 0 -> the GEMM list, 6 int32 per GEMM
