@@ -3,7 +3,7 @@
 #   build.sh          incremental: an object is rebuilt when the HASH of what it is made from changes
 #   build.sh --clean  from scratch
 # An object's stamp = sha256 of its own source, every header of csrc/ and include/, the compiler flags and hipcc's version.
-# The render variants (render_variants.sh) are one source, csrc/dfn_render_variant.hip, compiled once per variant through a
+# The render variants (csrc/dfn_render_variants.h, read by render_variants.sh) are one source, csrc/dfn_render_variant.hip, compiled once per variant through a
 # stub that build.sh writes into the build directory; a variant's own source is the stub (its defines) plus that file.
 # (Timestamps would reuse a stale object whenever a checkout puts an older header next to a newer .o: the objects travel
 # with the tree to the GPU box, the file times do not mean anything there.)

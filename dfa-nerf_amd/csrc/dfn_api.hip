@@ -367,119 +367,123 @@ int dfn_adam_multi(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int 
                                       (hipStream_t)stream), "adam_multi_kernel");
 }
 
+// The host-side requests of the fused launches: what an entry point was asked for, by name.  Each entry point fills one (value-
+// initialised: every member it does not name is null / 0 = off) and states the variant flags of its form (dfn_render_variants.h).
+// `who`: the name the shared checks report under - the texts callers match on.
+struct RenderReq {
+    const char* who;            // dfn_render_z_fwd for the z forms, dfn_render_fwd for every other one
+    int flags;                  // 0, TIER_AUX, TIER_RAYS or TIER_ZVALS (DFN_WIDTH_128 arrives in `tier`)
+    int tier;                   // the ABI's tier argument, its flags (DFN_WIDTH_128 / DFN_TRAIN_ACT_E4M3) still in it
+    const DfnFrame* frame;
+    const void *packed_head, *packed_torso;
+    const float *bias_head, *bias_torso, *bg_f32;
+    const uint8_t* bg_u8;
+    const int32_t* pix_index;
+    const float *rays, *bounds, *zvals;     // TIER_RAYS: f32 [ray_count, 6 * fields], [ray_count,2] or NULL; TIER_ZVALS: f32 [ray_count, n_coarse]
+    void *rgb_head, *rgb_com;   // f32, or uint8 with out_u8
+    int out_u8;
+    float *weights_head, *weights_com, *z_vals;
+    void *aux_head, *aux_com;   // TIER_AUX: f32 [ray_count,2], or alpha8 with out_u8
+    uint16_t *depth16_head, *depth16_com;
+    void* stream;
+};
+
 // What the inference and the training launch both set of a RenderArgs (value-initialised by the caller: all-zero is the "off"
 // state of every optional member): frame, blobs and slab counts, bias, backgrounds, pixel ids, rgb outputs.
-static int render_args(RenderArgs& A, const std::string& who, int tier, int width, const DfnFrame& F, const void* packed_head,
-                       const void* packed_torso, const float* bias_head, const float* bias_torso, const float* bg_f32,
-                       const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com) {
+// (a generic lambda: N is a RenderReq or a TrainReq, and a function template cannot stand inside extern "C")
+static const auto render_args = [](RenderArgs& A, const std::string& who, int tier, int width, const DfnFrame& F, const auto& N) -> int {
     // the kernel reads [head | torso] biases from one LDS image: they must be adjacent in memory
     ProgramInfo ph, pt;
     program_info(tier, FIELD_HEAD, &ph, width);
     program_info(tier, FIELD_TORSO, &pt, width);
-    if (F.fields == 2 && bias_torso != bias_head + ph.n_bias)
+    if (F.fields == 2 && N.bias_torso != N.bias_head + ph.n_bias)
         return fail(DFN_E_ARG, who + ": bias_torso must directly follow bias_head in memory");
     A.frame = F;
-    A.wblob[0] = (const char*)packed_head;
-    A.wblob[1] = (const char*)(F.fields == 2 ? packed_torso : packed_head);
+    A.wblob[0] = (const char*)N.packed_head;
+    A.wblob[1] = (const char*)(F.fields == 2 ? N.packed_torso : N.packed_head);
     A.nslab[0] = ph.n_slabs;
     A.nslab[1] = F.fields == 2 ? pt.n_slabs : ph.n_slabs;
-    A.bias = bias_head;
-    A.bg_f32 = bg_f32;
-    A.bg_u8 = bg_u8;
-    A.pix_index = pix_index;
-    A.rgb_head = rgb_head;
-    A.rgb_com = rgb_com;
+    A.bias = N.bias_head;
+    A.bg_f32 = N.bg_f32;
+    A.bg_u8 = N.bg_u8;
+    A.pix_index = N.pix_index;
+    A.rgb_head = (float*)N.rgb_head;
+    A.rgb_com = (float*)N.rgb_com;
     return DFN_OK;
-}
+};
 
-// the per-ray outputs of an aux launch (dfn_render_fwd_aux: head / com = f32 [ray_count,2]; dfn_render_fwd_u8_aux: head / com =
-// alpha8, d16_* = depth16)
-struct AuxOut {
-    void *head, *com, *d16_head, *d16_com;
-};
-// the per-ray inputs of a rays launch (dfn_render_rays_fwd[_u8]): rays f32 [ray_count, 6 * fields], bounds f32 [ray_count,2] or NULL
-struct RaysIn {
-    const float *rays, *bounds;
-};
-// the per-ray depths of a z launch (dfn_render_z_fwd[_u8]): f32 [ray_count, n_coarse]
-struct ZIn {
-    const float* zvals;
-};
-static int render_fwd_impl(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
-                           const float* bias_head, const float* bias_torso, const float* bg_f32,
-                           const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
-                           float* weights_head, float* weights_com, float* z_vals, int out_u8, void* stream,
-                           const AuxOut* aux = nullptr, const RaysIn* rin = nullptr, const ZIn* zin = nullptr) {
-    int width;
-    const std::string who = zin ? "dfn_render_z_fwd" : "dfn_render_fwd";      // the name the shared checks report under
-    if (take_width(tier, width, who.c_str()) != DFN_OK) return DFN_E_ARG;
-    // caller-supplied depths: the kernels exist in the inference tiers only, without an aux and without a rays form
-    if (zin && (tier == DFN_TIER_BF16 || aux || rin))
+static int render_fwd_impl(const RenderReq& q) {
+    const bool aux = q.flags == TIER_AUX, rin = q.flags == TIER_RAYS, zin = q.flags == TIER_ZVALS;
+    const std::string who = q.who;
+    int tier = q.tier, width;
+    if (take_width(tier, width, q.who) != DFN_OK) return DFN_E_ARG;
+    // caller-supplied depths: the kernels exist in the inference tiers only
+    if (zin && tier == DFN_TIER_BF16)
         return fail(DFN_E_ARG, "dfn_render_z_fwd: caller-supplied depths exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
                                "(bf16 is the training tier)");
-    if (zin && !zin->zvals) return fail(DFN_E_ARG, "dfn_render_z_fwd: zvals is NULL (dfn_render_fwd renders the frame's own linspace depths)");
-    // caller-supplied rays: the kernels exist in the inference tiers only, and without an aux form
-    if (rin && (tier == DFN_TIER_BF16 || aux))
+    if (zin && !q.zvals) return fail(DFN_E_ARG, "dfn_render_z_fwd: zvals is NULL (dfn_render_fwd renders the frame's own linspace depths)");
+    // caller-supplied rays: the kernels exist in the inference tiers only
+    if (rin && tier == DFN_TIER_BF16)
         return fail(DFN_E_ARG, "dfn_render_rays_fwd: caller-supplied rays exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
                                "(bf16 is the training tier)");
-    if (rin && !rin->rays) return fail(DFN_E_ARG, "dfn_render_rays_fwd: rays is NULL (dfn_render_fwd renders the frame's own pinhole rays)");
+    if (rin && !q.rays) return fail(DFN_E_ARG, "dfn_render_rays_fwd: rays is NULL (dfn_render_fwd renders the frame's own pinhole rays)");
     // the aux kernels exist in the inference tiers only (bf16 is the training tier)
     if (aux && tier == DFN_TIER_BF16)
         return fail(DFN_E_ARG, "dfn_render_fwd_aux: opacity / depth outputs exist in DFN_TIER_F32 / DFN_TIER_F16 / DFN_TIER_F16X3 only "
                                "(bf16 is the training tier)");
-    if (!tier_ok(tier) || !frame || !packed_head || !bias_head || !rgb_head)
-        return fail(DFN_E_ARG, who + ": bad argument");
-    const DfnFrame& F = *frame;
+    if (!tier_ok(tier) || !q.frame || !q.packed_head || !q.bias_head || !q.rgb_head) return fail(DFN_E_ARG, who + ": bad argument");
+    const DfnFrame& F = *q.frame;
     if ((zin ? z_counts_ok(F.n_coarse, F.n_fine, "dfn_render_z_fwd") : counts_ok(F.n_coarse, F.n_fine, "dfn_render_fwd")) != DFN_OK)
         return DFN_E_ARG;
     if (F.fields != 1 && F.fields != 2) return fail(DFN_E_ARG, who + ": fields must be 1 or 2");
-    if (F.fields == 2 && (!packed_torso || !bias_torso || !rgb_com))
+    if (F.fields == 2 && (!q.packed_torso || !q.bias_torso || !q.rgb_com))
         return fail(DFN_E_ARG, who + ": torso inputs / rgb_com missing for fields == 2");
-    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, who + ": no background given");
+    if (!q.bg_f32 && !q.bg_u8) return fail(DFN_E_ARG, who + ": no background given");
     if (F.ray_count <= 0) return DFN_OK;
     // (the z kernels address their per-sample arrays by 32-bit byte offsets)
     if (zin && (long)F.ray_count * F.n_coarse >= (1L << 30)) return fail(DFN_E_ARG, "dfn_render_z_fwd: too many rays per call (ray_count * n_coarse must stay under 2^30)");
     // (supplied rays: H, W, ray_begin, the intrinsics and the poses are ignored)
-    if (!rin && (F.H <= 0 || F.W <= 0 || (!pix_index && (F.ray_begin < 0 || F.ray_begin + F.ray_count > F.H * F.W))))
+    if (!rin && (F.H <= 0 || F.W <= 0 || (!q.pix_index && (F.ray_begin < 0 || F.ray_begin + F.ray_count > F.H * F.W))))
         return fail(DFN_E_ARG, who + ": ray range outside the image");
     RenderArgs A{};
-    const int rc = render_args(A, who, tier, width, F, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8,
-                               pix_index, rgb_head, rgb_com);
+    const int rc = render_args(A, who, tier, width, F, q);
     if (rc != DFN_OK) return rc;
-    A.w_head = weights_head;
-    A.w_com = weights_com;
-    A.z_out = z_vals;
-    A.out_u8 = out_u8;
-    if (aux) {       // the aux kernels write no per-sample output: its argument slots carry the per-ray ones (dfn_params.h)
-        A.aux = 1;
-        A.alpha8_head = (unsigned char*)aux->head;          // (= aux_head in the f32 form)
-        A.alpha8_com = (unsigned char*)aux->com;
-        A.depth16_head = (unsigned short*)aux->d16_head;
-        A.depth16_com = (unsigned short*)aux->d16_com;
+    A.out_u8 = q.out_u8;
+    // the shared slots, by the variant's flags (dfn_params.h)
+    if (aux) {
+        A.alpha8_head = (unsigned char*)q.aux_head;          // (= aux_head in the f32 form)
+        A.alpha8_com = (unsigned char*)q.aux_com;
+        A.depth16_head = q.depth16_head;
+        A.depth16_com = q.depth16_com;
+    } else {
+        A.w_head = q.weights_head;
+        A.w_com = q.weights_com;
+        A.z_out = q.z_vals;
     }
-    if (rin) {       // the rays kernels read no pixel id and record nothing: those argument slots carry the rays and the bounds (dfn_params.h)
-        A.use_rays = 1;
-        A.rays = rin->rays;
-        A.bounds = rin->bounds;
+    if (rin) {
+        A.rays = q.rays;
+        A.bounds = q.bounds;
     }
-    if (zin) A.zvals = zin->zvals;      // (an inference launch records no ranks: that argument slot carries the depths, dfn_params.h)
+    if (zin) A.zvals = q.zvals;
     A.clock_probe = g_clock_probe;
-    return launched(launch_render(tier, A, (hipStream_t)stream, width), "render_kernel");
+    return launched(launch_render(tier, q.flags | (width == 128 ? TIER_W128 : 0), A, (hipStream_t)q.stream), "render_kernel");
 }
 
 int dfn_render_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                    const float* bias_head, const float* bias_torso, const float* bg_f32,
                    const uint8_t* bg_u8, const int32_t* pix_index, float* rgb_head, float* rgb_com,
                    float* weights_head, float* weights_com, float* z_vals, void* stream) {
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
-                           rgb_head, rgb_com, weights_head, weights_com, z_vals, 0, stream);
+    return render_fwd_impl({.who = "dfn_render_fwd", .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                            .rgb_com = rgb_com, .weights_head = weights_head, .weights_com = weights_com, .z_vals = z_vals, .stream = stream});
 }
 
 int dfn_render_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                       const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                       const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream) {
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
-                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream);
+    return render_fwd_impl({.who = "dfn_render_fwd", .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb8_head,
+                            .rgb_com = rgb8_com, .out_u8 = 1, .stream = stream});
 }
 
 int dfn_render_fwd_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
@@ -488,9 +492,9 @@ int dfn_render_fwd_aux(int tier, const DfnFrame* frame, const void* packed_head,
     if (!aux_head) return fail(DFN_E_ARG, "dfn_render_fwd_aux: aux_head is NULL");
     if (frame && frame->fields == 2 && rgb_com && !aux_com)
         return fail(DFN_E_ARG, "dfn_render_fwd_aux: aux_com missing for fields == 2");
-    const AuxOut aux = {aux_head, aux_com, nullptr, nullptr};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
-                           rgb_head, rgb_com, nullptr, nullptr, nullptr, 0, stream, &aux);
+    return render_fwd_impl({.who = "dfn_render_fwd", .flags = TIER_AUX, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                            .rgb_com = rgb_com, .aux_head = aux_head, .aux_com = aux_com, .stream = stream});
 }
 
 int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
@@ -503,43 +507,46 @@ int dfn_render_fwd_u8_aux(int tier, const DfnFrame* frame, const void* packed_he
         return fail(DFN_E_ARG, "dfn_render_fwd_u8_aux: an output pair is selected by its _head pointer");
     if (frame && frame->fields == 2 && rgb8_com && ((alpha8_head && !alpha8_com) || (depth16_head && !depth16_com)))
         return fail(DFN_E_ARG, "dfn_render_fwd_u8_aux: alpha8_com / depth16_com missing for fields == 2");
-    const AuxOut aux = {alpha8_head, alpha8_com, depth16_head, depth16_com};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
-                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, &aux);
+    return render_fwd_impl({.who = "dfn_render_fwd", .flags = TIER_AUX, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb8_head,
+                            .rgb_com = rgb8_com, .out_u8 = 1, .aux_head = alpha8_head, .aux_com = alpha8_com, .depth16_head = depth16_head,
+                            .depth16_com = depth16_com, .stream = stream});
 }
 
 int dfn_render_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                         const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
                         const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* weights_head,
                         float* weights_com, float* z_vals, void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head,
-                           rgb_com, weights_head, weights_com, z_vals, 0, stream, nullptr, &rin);
+    return render_fwd_impl({.who = "dfn_render_fwd", .flags = TIER_RAYS, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .rays = rays, .bounds = bounds,
+                            .rgb_head = rgb_head, .rgb_com = rgb_com, .weights_head = weights_head, .weights_com = weights_com, .z_vals = z_vals,
+                            .stream = stream});
 }
 
 int dfn_render_rays_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                            const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
                            const float* bg_f32, const uint8_t* bg_u8, uint8_t* rgb8_head, uint8_t* rgb8_com, void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr,
-                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, nullptr, &rin);
+    return render_fwd_impl({.who = "dfn_render_fwd", .flags = TIER_RAYS, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                            .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .rays = rays, .bounds = bounds,
+                            .rgb_head = rgb8_head, .rgb_com = rgb8_com, .out_u8 = 1, .stream = stream});
 }
 
 int dfn_render_z_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                      const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                      const int32_t* pix_index, float* rgb_head, float* rgb_com, float* weights_head, float* weights_com,
                      float* z_vals, const float* zvals, void* stream) {
-    const ZIn zin = {zvals};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                           rgb_com, weights_head, weights_com, z_vals, 0, stream, nullptr, nullptr, &zin);
+    return render_fwd_impl({.who = "dfn_render_z_fwd", .flags = TIER_ZVALS, .tier = tier, .frame = frame, .packed_head = packed_head,
+                            .packed_torso = packed_torso, .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
+                            .pix_index = pix_index, .zvals = zvals, .rgb_head = rgb_head, .rgb_com = rgb_com, .weights_head = weights_head,
+                            .weights_com = weights_com, .z_vals = z_vals, .stream = stream});
 }
 
 int dfn_render_z_fwd_u8(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                         const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                         const int32_t* pix_index, uint8_t* rgb8_head, uint8_t* rgb8_com, const float* zvals, void* stream) {
-    const ZIn zin = {zvals};
-    return render_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index,
-                           (float*)rgb8_head, (float*)rgb8_com, nullptr, nullptr, nullptr, 1, stream, nullptr, nullptr, &zin);
+    return render_fwd_impl({.who = "dfn_render_z_fwd", .flags = TIER_ZVALS, .tier = tier, .frame = frame, .packed_head = packed_head,
+                            .packed_torso = packed_torso, .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
+                            .pix_index = pix_index, .zvals = zvals, .rgb_head = rgb8_head, .rgb_com = rgb8_com, .out_u8 = 1, .stream = stream});
 }
 
 int dfn_fine_depths(const DfnFrame* frame, const float* weights, float* z_all, void* stream) {
@@ -639,41 +646,59 @@ int dfn_train_prepare(int tier, const float* params, const float* signal_head, c
     return launched(launch_prepare(J, (hipStream_t)stream), "prepare_kernel");
 }
 
-static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
-                          const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
-                          const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
-                          uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all, uint8_t* ranks,
-                          bool hier, void* stream, const DfnTrainLoss* loss = nullptr, bool with_loss = false,
-                          const RaysIn* rin = nullptr) {
-    // rin: the step on caller-supplied rays (dfn_train_rays_fwd / _hier; no pixel ids, no _loss form)
-    const char* who = rin ? (hier ? "dfn_train_rays_fwd_hier" : "dfn_train_rays_fwd") : hier ? "dfn_train_fwd_hier" : "dfn_train_fwd";
+struct TrainReq {
+    const char* who;            // dfn_train[_rays]_fwd[_hier]; a _loss form reports under the name without _loss
+    int flags;                  // 0, or TIER_RAYS | TIER_TRAIN (DFN_TRAIN_ACT_E4M3 arrives in `tier`)
+    bool hier;
+    int tier;                   // the ABI's tier argument, its flags (DFN_WIDTH_128 / DFN_TRAIN_ACT_E4M3) still in it
+    const DfnFrame* frame;
+    const void *packed_head, *packed_torso;
+    const float *bias_head, *bias_torso, *bg_f32;
+    const uint8_t* bg_u8;
+    const int32_t* pix_index;
+    const float *rays, *bounds; // TIER_RAYS | TIER_TRAIN
+    float *rgb_head, *rgb_com;
+    float* samples;             // the recorder
+    void *act_head, *act_torso;
+    uint32_t *masks_head, *masks_torso;
+    float* z_all;               // hier
+    uint8_t* ranks;
+    bool with_loss;             // the _loss forms (no rays form)
+    const DfnTrainLoss* loss;
+    void* stream;
+};
+static int train_fwd_impl(const TrainReq& q) {
+    const bool rin = (q.flags & TIER_RAYS) != 0, hier = q.hier;
+    const std::string who = q.who;
+    const DfnFrame* frame = q.frame;
     // the format flag rides in the tier argument (include/dfanerf.h: DFN_TRAIN_ACT_E4M3); 16-bit tier only
-    if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;
+    int tier = q.tier;
+    if (no_width(tier, q.who) != DFN_OK) return DFN_E_ARG;
     const int act_e4m3 = (tier & DFN_TRAIN_ACT_E4M3) != 0;
     if (tier >= 0) tier &= ~DFN_TRAIN_ACT_E4M3;
-    if (act_e4m3 && tier != DFN_TIER_BF16) return fail(DFN_E_ARG, std::string(who) + ": DFN_TRAIN_ACT_E4M3 applies to DFN_TIER_BF16 only");
+    if (act_e4m3 && tier != DFN_TIER_BF16) return fail(DFN_E_ARG, who + ": DFN_TRAIN_ACT_E4M3 applies to DFN_TIER_BF16 only");
     if (rin) {
-        if (!rin->rays)
-            return fail(DFN_E_ARG, std::string(who) + ": rays is NULL (" + (hier ? "dfn_train_fwd_hier" : "dfn_train_fwd") +
-                                       " renders the frame's own pinhole rays)");
+        if (!q.rays)
+            return fail(DFN_E_ARG, who + ": rays is NULL (" + (hier ? "dfn_train_fwd_hier" : "dfn_train_fwd") + " renders the frame's own pinhole rays)");
         if (tier == DFN_TIER_F16 || tier == DFN_TIER_F16X3)
-            return fail(DFN_E_ARG, std::string(who) + ": DFN_TIER_F16 / DFN_TIER_F16X3 are inference only; the training step runs in "
-                                                      "DFN_TIER_F32 / DFN_TIER_BF16");
+            return fail(DFN_E_ARG, who + ": DFN_TIER_F16 / DFN_TIER_F16X3 are inference only; the training step runs in "
+                                         "DFN_TIER_F32 / DFN_TIER_BF16");
         if (frame && frame->fields != 2)
-            return fail(DFN_E_ARG, std::string(who) + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, "
-                                                      "o_torso, d_torso)");
+            return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, "
+                                         "o_torso, d_torso)");
         if (frame && !hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
-            return fail(DFN_E_ARG, std::string(who) + ": 32, 64 or 128 coarse samples, no fine ones (dfn_train_rays_fwd_hier is the "
-                                                      "hierarchical variant)");
+            return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (dfn_train_rays_fwd_hier is the "
+                                         "hierarchical variant)");
         if (frame && hier && frame->n_fine == 0)
-            return fail(DFN_E_ARG, std::string(who) + ": n_fine > 0 (dfn_train_rays_fwd is the coarse-only step)");
+            return fail(DFN_E_ARG, who + ": n_fine > 0 (dfn_train_rays_fwd is the coarse-only step)");
     }
-    if (with_loss && (!loss || !loss->img_head || !loss->img_com || !loss->d_rgb_head || !loss->d_rgb_com || !loss->losses ||
-                      !loss->workspace))
-        return fail(DFN_E_ARG, std::string(who) + "_loss: bad loss argument");
-    if (!train_tier_ok(tier) || !frame || !packed_head || !packed_torso || !bias_head || !bias_torso || !rgb_head ||
-        !rgb_com || !samples || !act_head || !masks_head || !act_torso || !masks_torso || (hier && (!z_all || !ranks)))
-        return fail(DFN_E_ARG, std::string(who) + ": bad argument");
+    const DfnTrainLoss* loss = q.loss;
+    if (q.with_loss && (!loss || !loss->img_head || !loss->img_com || !loss->d_rgb_head || !loss->d_rgb_com || !loss->losses ||
+                        !loss->workspace))
+        return fail(DFN_E_ARG, who + "_loss: bad loss argument");
+    if (!train_tier_ok(tier) || !frame || !q.packed_head || !q.packed_torso || !q.bias_head || !q.bias_torso || !q.rgb_head ||
+        !q.rgb_com || !q.samples || !q.act_head || !q.masks_head || !q.act_torso || !q.masks_torso || (hier && (!q.z_all || !q.ranks)))
+        return fail(DFN_E_ARG, who + ": bad argument");
     const DfnFrame& F = *frame;
     if (!hier && (!coarse_ok(F.n_coarse) || F.n_fine != 0 || F.fields != 2))
         return fail(DFN_E_ARG, "dfn_train_fwd: the training step is coarse-only (64 samples), two fields (MAIN:855-899); "
@@ -681,33 +706,31 @@ static int train_fwd_impl(int tier, const DfnFrame* frame, const void* packed_he
     // (the forward records at every pair the renderer takes - the f16 guards calibrate through it; the backward is 64 + 64 | 128)
     if (hier && (F.n_fine == 0 || F.fields != 2))
         return fail(DFN_E_ARG, "dfn_train_fwd_hier: n_fine > 0 (dfn_train_fwd is the coarse-only step), two fields");
-    if (hier && counts_ok(F.n_coarse, F.n_fine, who) != DFN_OK) return DFN_E_ARG;
-    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, std::string(who) + ": no background given");
+    if (hier && counts_ok(F.n_coarse, F.n_fine, q.who) != DFN_OK) return DFN_E_ARG;
+    if (!q.bg_f32 && !q.bg_u8) return fail(DFN_E_ARG, who + ": no background given");
     if (F.ray_count <= 0) return DFN_OK;
     const long NP = (long)F.ray_count * (F.n_coarse + F.n_fine);
-    if (dfn_train_rows(1, 0) * NP >= (1L << 32)) return fail(DFN_E_ARG, std::string(who) + ": too many rays per call");
+    if (dfn_train_rows(1, 0) * NP >= (1L << 32)) return fail(DFN_E_ARG, who + ": too many rays per call");
     RenderArgs A{};
-    const int rc = render_args(A, who, tier, 256, F, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                               rgb_com);
+    const int rc = render_args(A, who, tier, 256, F, q);
     if (rc != DFN_OK) return rc;
     if (hier) {
-        A.z_out = z_all;
-        A.ranks_out = ranks;
+        A.z_out = q.z_all;
+        A.ranks_out = q.ranks;
     }
-    A.samples_out = samples;
-    A.act_T[0] = act_head;
-    A.act_T[1] = act_torso;
-    A.masks[0] = masks_head;
-    A.masks[1] = masks_torso;
+    A.samples_out = q.samples;
+    A.act_T[0] = q.act_head;
+    A.act_T[1] = q.act_torso;
+    A.masks[0] = q.masks_head;
+    A.masks[1] = q.masks_torso;
     A.NP = NP;
     A.act_e4m3 = act_e4m3;
-    if (with_loss) A.loss = *loss;
-    if (rin) {       // the recorder owns samples_out: the bounds ride in the w_head slot, which a training launch leaves null (dfn_params.h)
-        A.use_rays = 2;
-        A.rays = rin->rays;             // (the pix_index slot)
-        A.train_bounds = rin->bounds;
+    if (q.with_loss) A.loss = *loss;
+    if (rin) {       // the shared slots of TIER_RAYS | TIER_TRAIN (dfn_params.h)
+        A.rays = q.rays;
+        A.train_bounds = q.bounds;
     }
-    return launched(launch_render(tier, A, (hipStream_t)stream), "render_kernel(train)");
+    return launched(launch_render(tier, q.flags | (act_e4m3 ? TIER_E4M3 : 0), A, (hipStream_t)q.stream), "render_kernel(train)");
 }
 
 // per-workgroup partial sums [2][workgroups] + the ticket; a workgroup renders at least 4 rays in every tier
@@ -716,26 +739,30 @@ int dfn_train_fwd_loss(int tier, const DfnFrame* frame, const void* packed_head,
                        const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                        const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                        uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, const DfnTrainLoss* loss, void* stream) {
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                          rgb_com, samples, act_head, masks_head, act_torso, masks_torso, nullptr, nullptr, false, stream,
-                          loss, true);
+    return train_fwd_impl({.who = "dfn_train_fwd", .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                           .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                           .rgb_com = rgb_com, .samples = samples, .act_head = act_head, .act_torso = act_torso, .masks_head = masks_head,
+                           .masks_torso = masks_torso, .with_loss = true, .loss = loss, .stream = stream});
 }
 int dfn_train_fwd_hier_loss(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                             const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                             const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                             uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all, uint8_t* ranks,
                             const DfnTrainLoss* loss, void* stream) {
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                          rgb_com, samples, act_head, masks_head, act_torso, masks_torso, z_all, ranks, true, stream, loss,
-                          true);
+    return train_fwd_impl({.who = "dfn_train_fwd_hier", .hier = true, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                           .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                           .rgb_com = rgb_com, .samples = samples, .act_head = act_head, .act_torso = act_torso, .masks_head = masks_head,
+                           .masks_torso = masks_torso, .z_all = z_all, .ranks = ranks, .with_loss = true, .loss = loss, .stream = stream});
 }
 
 int dfn_train_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                   const float* bias_head, const float* bias_torso, const float* bg_f32, const uint8_t* bg_u8,
                   const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                   uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, void* stream) {
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                          rgb_com, samples, act_head, masks_head, act_torso, masks_torso, nullptr, nullptr, false, stream);
+    return train_fwd_impl({.who = "dfn_train_fwd", .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                           .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                           .rgb_com = rgb_com, .samples = samples, .act_head = act_head, .act_torso = act_torso, .masks_head = masks_head,
+                           .masks_torso = masks_torso, .stream = stream});
 }
 
 int dfn_train_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
@@ -743,17 +770,20 @@ int dfn_train_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head,
                        const int32_t* pix_index, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                        uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all, uint8_t* ranks,
                        void* stream) {
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, pix_index, rgb_head,
-                          rgb_com, samples, act_head, masks_head, act_torso, masks_torso, z_all, ranks, true, stream);
+    return train_fwd_impl({.who = "dfn_train_fwd_hier", .hier = true, .tier = tier, .frame = frame, .packed_head = packed_head, .packed_torso = packed_torso,
+                           .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .pix_index = pix_index, .rgb_head = rgb_head,
+                           .rgb_com = rgb_com, .samples = samples, .act_head = act_head, .act_torso = act_torso, .masks_head = masks_head,
+                           .masks_torso = masks_torso, .z_all = z_all, .ranks = ranks, .stream = stream});
 }
 
 int dfn_train_rays_fwd(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
                        const float* bias_head, const float* bias_torso, const float* rays, const float* bounds,
                        const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples, void* act_head,
                        uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head, rgb_com,
-                          samples, act_head, masks_head, act_torso, masks_torso, nullptr, nullptr, false, stream, nullptr, false, &rin);
+    return train_fwd_impl({.who = "dfn_train_rays_fwd", .flags = TIER_RAYS | TIER_TRAIN, .tier = tier, .frame = frame, .packed_head = packed_head,
+                           .packed_torso = packed_torso, .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .rays = rays,
+                           .bounds = bounds, .rgb_head = rgb_head, .rgb_com = rgb_com, .samples = samples, .act_head = act_head, .act_torso = act_torso,
+                           .masks_head = masks_head, .masks_torso = masks_torso, .stream = stream});
 }
 
 int dfn_train_rays_fwd_hier(int tier, const DfnFrame* frame, const void* packed_head, const void* packed_torso,
@@ -761,9 +791,10 @@ int dfn_train_rays_fwd_hier(int tier, const DfnFrame* frame, const void* packed_
                             const float* bg_f32, const uint8_t* bg_u8, float* rgb_head, float* rgb_com, float* samples,
                             void* act_head, uint32_t* masks_head, void* act_torso, uint32_t* masks_torso, float* z_all,
                             uint8_t* ranks, void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return train_fwd_impl(tier, frame, packed_head, packed_torso, bias_head, bias_torso, bg_f32, bg_u8, nullptr, rgb_head, rgb_com,
-                          samples, act_head, masks_head, act_torso, masks_torso, z_all, ranks, true, stream, nullptr, false, &rin);
+    return train_fwd_impl({.who = "dfn_train_rays_fwd_hier", .flags = TIER_RAYS | TIER_TRAIN, .hier = true, .tier = tier, .frame = frame,
+                           .packed_head = packed_head, .packed_torso = packed_torso, .bias_head = bias_head, .bias_torso = bias_torso, .bg_f32 = bg_f32,
+                           .bg_u8 = bg_u8, .rays = rays, .bounds = bounds, .rgb_head = rgb_head, .rgb_com = rgb_com, .samples = samples, .act_head = act_head,
+                           .act_torso = act_torso, .masks_head = masks_head, .masks_torso = masks_torso, .z_all = z_all, .ranks = ranks, .stream = stream});
 }
 
 int dfn_sample_pixels(int H, int W, int n, int rect_num, const int32_t* rect, uint64_t seed, uint64_t counter,
@@ -783,19 +814,31 @@ int dfn_mse_loss_u8(const float* rgb_head, const float* rgb_com, const uint8_t* 
                                     (hipStream_t)stream), "mse_loss_kernel");
 }
 
-static int composite_bwd_impl(bool hier, const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
-                              const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
-                              const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream,
-                              const RaysIn* rin = nullptr) {
-    // rin: the step on caller-supplied rays (dfn_composite_bwd_rays_z / _hier_rays_z; no pixel ids)
-    const std::string who = rin ? (hier ? "dfn_composite_bwd_hier_rays_z" : "dfn_composite_bwd_rays_z") : hier ? "dfn_composite_bwd_hier" : "dfn_composite_bwd";
-    if (rin && !rin->rays)
+struct BwdReq {
+    const char* who;            // the entry point; the _z forms of the pixel-id step report under the name without _z
+    bool hier, on_rays;         // on_rays: the step on caller-supplied rays (dfn_composite_bwd[_hier]_rays_z; no pixel ids)
+    const DfnFrame* frame;
+    const int32_t* pix_index;
+    const float *rays, *bounds, *bg_f32;
+    const uint8_t* bg_u8;
+    const float *samples, *z_all;
+    const uint8_t* ranks;
+    const float *d_rgb_head, *d_rgb_com;
+    float *dsamples, *zero_buf;
+    long zero_floats;
+    void* stream;
+};
+static int composite_bwd_impl(const BwdReq& q) {
+    const bool hier = q.hier, rin = q.on_rays;
+    const std::string who = q.who;
+    const DfnFrame* frame = q.frame;
+    if (rin && !q.rays)
         return fail(DFN_E_ARG, who + ": rays is NULL (" + (hier ? "dfn_composite_bwd_hier_z" : "dfn_composite_bwd_z") +
                                    " rebuilds the frame's own pinhole rays)");
-    if (rin && zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
+    if (rin && q.zero_buf && (((unsigned long)q.zero_buf & 15) || q.zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
     if (rin && frame && frame->fields != 2)
         return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
-    if (!frame || !samples || (hier && (!z_all || !ranks)) || !d_rgb_head || !dsamples || (!bg_f32 && !bg_u8))
+    if (!frame || !q.samples || (hier && (!q.z_all || !q.ranks)) || !q.d_rgb_head || !q.dsamples || (!q.bg_f32 && !q.bg_u8))
         return fail(DFN_E_ARG, who + ": bad argument");
     if (hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
         return fail(DFN_E_ARG, who + ": 64 coarse + 64 or 128 fine samples");
@@ -804,68 +847,72 @@ static int composite_bwd_impl(bool hier, const DfnFrame* frame, const int32_t* p
     if (frame->ray_count <= 0) return DFN_OK;
     CompositeBwdRaysArgs A{};           // (the plain launches take its base: the block they have always had)
     A.frame = *frame;
-    A.pix_index = pix_index;
-    A.bg_f32 = bg_f32;
-    A.bg_u8 = bg_u8;
-    A.samples = samples;
-    A.d_rgb_head = d_rgb_head;
-    A.d_rgb_com = d_rgb_com;
-    A.dsamples = dsamples;
-    A.z_all = z_all;            // (hierarchical step only)
-    A.ranks = ranks;
-    A.zero_buf = zero_buf;
-    A.zero_floats = zero_buf ? zero_floats : 0;
+    A.pix_index = q.pix_index;
+    A.bg_f32 = q.bg_f32;
+    A.bg_u8 = q.bg_u8;
+    A.samples = q.samples;
+    A.d_rgb_head = q.d_rgb_head;
+    A.d_rgb_com = q.d_rgb_com;
+    A.dsamples = q.dsamples;
+    A.z_all = q.z_all;            // (hierarchical step only)
+    A.ranks = q.ranks;
+    A.zero_buf = q.zero_buf;
+    A.zero_floats = q.zero_buf ? q.zero_floats : 0;
+    hipStream_t st = (hipStream_t)q.stream;
     if (rin) {
-        A.rays = rin->rays;
-        A.bounds = rin->bounds;
-        return launched(launch_composite_bwd_rays(A, hier, (hipStream_t)stream), hier ? "composite_bwd_hier_kernel(rays)" : "composite_bwd_kernel(rays)");
+        A.rays = q.rays;
+        A.bounds = q.bounds;
+        return launched(launch_composite_bwd_rays(A, hier, st), hier ? "composite_bwd_hier_kernel(rays)" : "composite_bwd_kernel(rays)");
     }
-    if (hier) return launched(launch_composite_bwd_hier(A, (hipStream_t)stream), "composite_bwd_hier_kernel");
-    return launched(launch_composite_bwd(A, (hipStream_t)stream), "composite_bwd_kernel");
+    if (hier) return launched(launch_composite_bwd_hier(A, st), "composite_bwd_hier_kernel");
+    return launched(launch_composite_bwd(A, st), "composite_bwd_kernel");
 }
 int dfn_composite_bwd(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                       const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
                       void* stream) {
-    return composite_bwd_impl(false, frame, pix_index, bg_f32, bg_u8, samples, nullptr, nullptr, d_rgb_head, d_rgb_com, dsamples,
-                              nullptr, 0, stream);
+    return composite_bwd_impl({.who = "dfn_composite_bwd", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples,
+                               .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .stream = stream});
 }
 int dfn_composite_bwd_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                         const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
                         float* zero_buf, long zero_floats, void* stream) {
     if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0))
         return fail(DFN_E_ARG, "dfn_composite_bwd_z: zero_buf must be 16-byte aligned");
-    return composite_bwd_impl(false, frame, pix_index, bg_f32, bg_u8, samples, nullptr, nullptr, d_rgb_head, d_rgb_com, dsamples,
-                              zero_buf, zero_floats, stream);
+    return composite_bwd_impl({.who = "dfn_composite_bwd", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples,
+                               .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats,
+                               .stream = stream});
 }
 int dfn_composite_bwd_hier(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                            const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
                            const float* d_rgb_com, float* dsamples, void* stream) {
-    return composite_bwd_impl(true, frame, pix_index, bg_f32, bg_u8, samples, z_all, ranks, d_rgb_head, d_rgb_com, dsamples, nullptr, 0,
-                              stream);
+    return composite_bwd_impl({.who = "dfn_composite_bwd_hier", .hier = true, .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
+                               .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
+                               .stream = stream});
 }
 int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
                              const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
                              const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream) {
     if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0))
         return fail(DFN_E_ARG, "dfn_composite_bwd_hier_z: zero_buf must be 16-byte aligned");
-    return composite_bwd_impl(true, frame, pix_index, bg_f32, bg_u8, samples, z_all, ranks, d_rgb_head, d_rgb_com, dsamples, zero_buf,
-                              zero_floats, stream);
+    return composite_bwd_impl({.who = "dfn_composite_bwd_hier", .hier = true, .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
+                               .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
+                               .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
 }
 
 int dfn_composite_bwd_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
                              const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
                              long zero_floats, void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return composite_bwd_impl(false, frame, nullptr, bg_f32, bg_u8, samples, nullptr, nullptr, d_rgb_head, d_rgb_com, dsamples, zero_buf,
-                              zero_floats, stream, &rin);
+    return composite_bwd_impl({.who = "dfn_composite_bwd_rays_z", .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds, .bg_f32 = bg_f32,
+                               .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf,
+                               .zero_floats = zero_floats, .stream = stream});
 }
 int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
                                   void* stream) {
-    const RaysIn rin = {rays, bounds};
-    return composite_bwd_impl(true, frame, nullptr, bg_f32, bg_u8, samples, z_all, ranks, d_rgb_head, d_rgb_com, dsamples, zero_buf,
-                              zero_floats, stream, &rin);
+    return composite_bwd_impl({.who = "dfn_composite_bwd_hier_rays_z", .hier = true, .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds,
+                               .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head,
+                               .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
 }
 
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,
@@ -1186,7 +1233,7 @@ static int decoder_impl(int tier, int width, int field, const void* packed, cons
     A.samples = samples;
     A.act_T = act_T;
     A.masks = masks;
-    return launched(launch_decoder(tier, A, (hipStream_t)stream, width), what);
+    return launched(launch_decoder(tier, width == 128 ? TIER_W128 : 0, A, (hipStream_t)stream), what);
 }
 
 int dfn_decoder_fwd(int tier, int field, const void* packed, const float* bias, const float* points,

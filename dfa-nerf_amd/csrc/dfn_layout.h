@@ -47,11 +47,11 @@ constexpr int TIER_RAYS = 0x800;
 // sample depths from memory instead of spacing them between near and far; coarse-only launches of 32 ... 192 samples.  Never with
 // TIER_AUX or TIER_RAYS
 constexpr int TIER_ZVALS = 0x1000;
-// a flag of the render variants (dfn_render_variant.hip) only - it never reaches a kernel's first template argument: the 16-bit
-// training forwards whose recorder writes e4m3 (render_kernel<.., ACT4 = false>: RenderArgs.act_e4m3)
+// a flag of the render variants (dfn_render_variants.h) only - it never reaches a kernel's first template argument: the 16-bit
+// training forwards whose recorder writes e4m3 (render_kernel<.., ACT4 = false>)
 constexpr int TIER_E4M3 = 0x100;
 // a flag of the render variants only, the same way: the training forwards on caller-supplied rays (dfn_train_rays_fwd / _hier;
-// render_kernel<TIER | TIER_RAYS, true, TRAIN = 1, 2>: RenderArgs.use_rays == 2).  Always with TIER_RAYS; with TIER_E4M3 in the bf16 tier
+// render_kernel<TIER | TIER_RAYS, true, TRAIN = 1, 2>).  Always with TIER_RAYS; with TIER_E4M3 in the bf16 tier
 // for the e4m3 recorder
 constexpr int TIER_TRAIN = 0x2000;
 DFN_HD constexpr bool tier_trainable(int tier) { return tier == TIER_F32 || tier == TIER_BF16; }    // has training kernels (recorder on)

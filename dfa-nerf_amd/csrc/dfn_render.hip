@@ -1,6 +1,6 @@
-// dfn_render.hip - tier, width and mode dispatch of the fused frame renderer and the fused decoder.
-// The kernels are templates in dfn_render_kernels.h; each render variant (a tier and a set of flags) is an object of its own,
-// compiled from dfn_render_variant.hip (its header describes the scheme).  This file holds the library's list of them.
+// dfn_render.hip - dispatch of the fused frame renderer and the fused decoder by variant key (tier, flags).
+// The kernels are templates in dfn_render_kernels.h; each render variant is an object of its own, compiled from
+// dfn_render_variant.hip.  The list of them is dfn_render_variants.h; this file turns it into the lookup table.
 #include <hip/hip_runtime.h>
 #include "dfn_layout.h"
 #include "dfn_mlp.h"
@@ -8,50 +8,42 @@
 
 namespace dfn {
 
-// ---- the variant list: X(tier, flags), one object each (the build's side of it: render_variants.sh) ----
-#define DFN_INFERENCE_VARIANTS(X, T) \
-    X(T, 0) X(T, TIER_W128) X(T, TIER_AUX) X(T, TIER_W128 | TIER_AUX) X(T, TIER_RAYS) X(T, TIER_W128 | TIER_RAYS) \
-    X(T, TIER_ZVALS) X(T, TIER_W128 | TIER_ZVALS)
-#define DFN_RENDER_VARIANTS(X) \
-    DFN_INFERENCE_VARIANTS(X, TIER_F32) DFN_INFERENCE_VARIANTS(X, TIER_F16) DFN_INFERENCE_VARIANTS(X, TIER_F16X3) \
-    X(TIER_BF16, 0) X(TIER_BF16, TIER_E4M3) \
-    X(TIER_F32, TIER_RAYS | TIER_TRAIN) X(TIER_BF16, TIER_RAYS | TIER_TRAIN) X(TIER_BF16, TIER_RAYS | TIER_TRAIN | TIER_E4M3)
-
+// ---- the variant table: one entry per line of dfn_render_variants.h, keyed by (tier, flags) ----
 struct Variant {
+    int tier, flags;
     hipError_t (*render)(const RenderArgs&, hipStream_t);
     hipError_t (*decoder)(const DecoderArgs&, hipStream_t);
 };
-enum Mode { MODE_PLAIN, MODE_AUX, MODE_RAYS, MODE_E4M3, MODE_ZVALS, MODE_RAYS_TRAIN, MODE_RAYS_TRAIN_E4M3, N_MODES };
-constexpr int N_TIERS = TIER_F16X3 + 1;
-struct VariantTable { Variant at[N_TIERS][2][N_MODES]; };         // [tier][width == 128][mode]; no such variant: null
-static constexpr VariantTable make_table() {
-    VariantTable t{};
-#define X(T, F) \
-    t.at[T][((F) & TIER_W128) != 0][(F) & TIER_TRAIN ? ((F) & TIER_E4M3 ? MODE_RAYS_TRAIN_E4M3 : MODE_RAYS_TRAIN) : (F) & TIER_RAYS ? MODE_RAYS : (F) & TIER_ZVALS ? MODE_ZVALS : (F) & TIER_AUX ? MODE_AUX : (F) & TIER_E4M3 ? MODE_E4M3 : MODE_PLAIN] = \
-        {launch_render_tier<T, (F)>, launch_decoder_tier<T, (F)>};
-    DFN_RENDER_VARIANTS(X)
-#undef X
-    return t;
+static constexpr Variant VARIANTS[] = {
+#define DFN_VARIANT(name, tier, flags) {tier, (flags), launch_render_tier<tier, (flags)>, launch_decoder_tier<tier, (flags)>},
+#include "dfn_render_variants.h"
+#undef DFN_VARIANT
+};
+static constexpr const Variant* variant(int tier, int flags) {
+    for (const Variant& v : VARIANTS)
+        if (v.tier == tier && v.flags == flags) return &v;
+    return nullptr;
 }
-static constexpr VariantTable TABLE = make_table();
-static const Variant* variant(int tier, int width, int mode) {
-    if (tier < 0 || tier >= N_TIERS) return nullptr;
-    return &TABLE.at[tier][width == 128][mode];
+static constexpr bool keys_unique() {       // every entry is what the lookup finds for its key: no two entries share one
+    for (const Variant& v : VARIANTS)
+        if (variant(v.tier, v.flags) != &v) return false;
+    return true;
 }
+static_assert(keys_unique(), "dfn_render_variants.h: two variants with the same (tier, flags)");
+// keys that must not exist (the API refuses them before; a launch with one is hipErrorInvalidValue): bf16 is the training tier -
+// no aux, rays, z or 128-wide form; the f16 tiers are inference only
+static_assert(!variant(TIER_BF16, TIER_AUX) && !variant(TIER_BF16, TIER_RAYS) && !variant(TIER_BF16, TIER_ZVALS) && !variant(TIER_BF16, TIER_W128),
+              "bf16: training tier");
+static_assert(!variant(TIER_F16, TIER_RAYS | TIER_TRAIN) && !variant(TIER_F16X3, TIER_RAYS | TIER_TRAIN) && !variant(TIER_F16, TIER_E4M3),
+              "f16 / f16x3: inference only");
 
-hipError_t launch_render(int tier, const RenderArgs& A, hipStream_t st, int width) {
-    // rays first: a rays launch carries `bounds` in the recorder's samples_out slot (bf16: refused by the API); then aux (bf16 has no
-    // aux kernels; the API refuses it before); then the width (bf16: the training tier stays padded; the API refuses it before).
-    // The 16-bit training step with the e4m3 opt-out for act_T: those two kernels are a variant of their own.  A z launch: `zvals` shares
-    // the argument slot of the recorder's ranks_out and of the aux route's depth16_com - it is one when neither of those is on.
-    // use_rays == 2: the training forward on caller-supplied rays (recorder on, bounds in the w_head slot): variants of their own
-    const int mode = A.use_rays == 2 ? (tier == TIER_BF16 && A.act_e4m3 ? MODE_RAYS_TRAIN_E4M3 : MODE_RAYS_TRAIN) : A.use_rays ? MODE_RAYS : A.aux ? MODE_AUX : (!A.samples_out && A.zvals) ? MODE_ZVALS : (tier == TIER_BF16 && A.samples_out && A.act_e4m3) ? MODE_E4M3 : MODE_PLAIN;
-    const Variant* v = variant(tier, width, mode);
-    return v && v->render ? v->render(A, st) : hipErrorInvalidValue;
+hipError_t launch_render(int tier, int flags, const RenderArgs& A, hipStream_t st) {
+    const Variant* v = variant(tier, flags);
+    return v ? v->render(A, st) : hipErrorInvalidValue;
 }
-hipError_t launch_decoder(int tier, const DecoderArgs& A, hipStream_t st, int width) {
-    const Variant* v = variant(tier, width, MODE_PLAIN);
-    return v && v->decoder ? v->decoder(A, st) : hipErrorInvalidValue;
+hipError_t launch_decoder(int tier, int flags, const DecoderArgs& A, hipStream_t st) {
+    const Variant* v = variant(tier, flags);
+    return v ? v->decoder(A, st) : hipErrorInvalidValue;
 }
 
 // the 16-bit tiers share one program (same fragment counts and bias blob)

@@ -934,31 +934,26 @@ template <int TIER, bool TORSO, bool REC = false, int W128 = 0> static hipError_
     return hipGetLastError();
 }
 
-// every launch of one render variant (tier, flags: dfn_render_variant.hip).  FLAGS == 0: the 256-wide program of the tier - inference
-// and, in a trainable tier, the training forwards (recorder on).  Every other variant is inference only and holds the kernels of its
-// flags alone: TIER_W128 (the API refuses DFN_WIDTH_128 in every training entry point), TIER_AUX (dfn_render_fwd_aux /
-// dfn_render_fwd_u8_aux), TIER_RAYS (dfn_render_rays_fwd / dfn_render_rays_fwd_u8; the recorder's samples_out slot carries `bounds`),
-// TIER_ZVALS (dfn_render_z_fwd / dfn_render_z_fwd_u8; the recorder's ranks_out slot carries `zvals`), the last three with or without
-// TIER_W128.  TIER_E4M3: the two 16-bit training forwards whose recorder writes act_T as MX-fp8 e4m3
-// (the run-time opt-out of the narrow activation format, for A/B runs of the two formats on real data in one process), nothing else.
-// TIER_RAYS | TIER_TRAIN [| TIER_E4M3]: the two training forwards on caller-supplied rays (dfn_train_rays_fwd / _hier: RenderArgs.use_rays
-// == 2, recorder on), in a trainable tier; with TIER_E4M3 (bf16) the ones whose recorder writes e4m3.  Nothing else.
+// every launch of one render variant (tier, flags: dfn_render_variants.h lists them and says what each flag's unit holds).  The
+// caller has stated the variant (launch_render, dfn_render.hip); what is chosen here is what varies WITHIN one: one or two fields,
+// n_fine > 0, and in the flags-0 unit of a trainable tier whether the recorder is on.  The checks are the pointers and shapes the
+// variant's kernels rely on.
 template <int TIER, int FLAGS> hipError_t launch_render_tier(const RenderArgs& A, hipStream_t st) {
     if constexpr ((FLAGS & TIER_TRAIN) != 0) {
         static_assert((FLAGS & ~TIER_E4M3) == (TIER_RAYS | TIER_TRAIN) && tier_trainable(TIER), "TIER_TRAIN: the rays training forwards");
         static_assert((FLAGS & TIER_E4M3) == 0 || TIER == TIER_BF16, "the e4m3 recorder is the bf16 tier's");
         constexpr bool ACT4 = (FLAGS & TIER_E4M3) == 0;
-        if (A.use_rays != 2 || !A.rays || !A.samples_out || A.aux || A.frame.fields != 2 || A.loss.losses) return hipErrorInvalidValue;
+        if (!A.rays || !A.samples_out || A.frame.fields != 2 || A.loss.losses) return hipErrorInvalidValue;
         return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2, ACT4, TIER_RAYS>(A, st) : launch_render_t<TIER, true, 1, ACT4, TIER_RAYS>(A, st);
     } else if constexpr (FLAGS == TIER_E4M3) {
         return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2, false>(A, st) : launch_render_t<TIER, true, 1, false>(A, st);
     } else {
         if constexpr ((FLAGS & TIER_RAYS) != 0) {
-            if (A.use_rays != 1 || A.aux || !A.rays) return hipErrorInvalidValue;
+            if (!A.rays) return hipErrorInvalidValue;
         } else if constexpr ((FLAGS & TIER_ZVALS) != 0) {
-            if (A.samples_out || A.aux || A.use_rays || !A.zvals || A.frame.n_fine != 0) return hipErrorInvalidValue;
+            if (A.samples_out || !A.zvals || A.frame.n_fine != 0) return hipErrorInvalidValue;
         } else if constexpr ((FLAGS & TIER_AUX) != 0) {
-            if (A.samples_out || !A.aux) return hipErrorInvalidValue;
+            if (A.samples_out) return hipErrorInvalidValue;
         } else if (A.samples_out) {     // training step: two fields, recorder on; coarse only (MAIN:855-899) or hierarchical (row H)
             if constexpr (FLAGS == 0 && tier_trainable(TIER))
                 return A.frame.n_fine > 0 ? launch_render_t<TIER, true, 2>(A, st) : launch_render_t<TIER, true, 1>(A, st);

@@ -214,6 +214,14 @@ class FusedTrainRaysFn(torch.autograd.Function):
         return _fused_backward(ctx, d_h, d_c) + (None,)       # (one input more than FusedTrainFn: rays, bounds for pix_index)
 
 
+# the fused step's entry points: forward by (caller-supplied rays, hierarchical, loss epilogue), compositing backward by the first two
+_FWD_ENTRY = {(False, False, False): "dfn_train_fwd", (False, True, False): "dfn_train_fwd_hier",
+              (False, False, True): "dfn_train_fwd_loss", (False, True, True): "dfn_train_fwd_hier_loss",
+              (True, False, False): "dfn_train_rays_fwd", (True, True, False): "dfn_train_rays_fwd_hier"}
+_BWD_ENTRY = {(False, False): "dfn_composite_bwd_z", (False, True): "dfn_composite_bwd_hier_z",
+              (True, False): "dfn_composite_bwd_rays_z", (True, True): "dfn_composite_bwd_hier_rays_z"}
+
+
 def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None, rays=None, bounds=None):
     # rays / bounds: the step on caller-supplied rays (FusedTrainRaysFn; no pixel ids, no loss epilogue)
     # loss: a _lib.DfnTrainLoss -> the forward's epilogue forms the step's loss and d loss / d rgb (dfn_train_fwd*_loss)
@@ -237,37 +245,18 @@ def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape,
     rgb_c = torch.empty(n, 3, dtype=torch.float32, device=dev)
     bg_f32 = bg if bg.dtype == torch.float32 else None
     bg_u8 = bg if bg.dtype == torch.uint8 else None
-    if rays is not None and buf.n_fine:
-        check(lib.dfn_train_rays_fwd_hier(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                          _ptr(rays), _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c),
-                                          _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                          _ptr(buf.masks[1]), _ptr(buf.z_all), _ptr(buf.ranks), st), "dfn_train_rays_fwd_hier")
-    elif rays is not None:
-        check(lib.dfn_train_rays_fwd(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                     _ptr(rays), _ptr(bounds), _ptr(bg_f32), _ptr(bg_u8), _ptr(rgb_h), _ptr(rgb_c),
-                                     _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                     _ptr(buf.masks[1]), st), "dfn_train_rays_fwd")
-    elif loss is not None and buf.n_fine:
-        check(lib.dfn_train_fwd_hier_loss(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                          _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c),
-                                          _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                          _ptr(buf.masks[1]), _ptr(buf.z_all), _ptr(buf.ranks), C.byref(loss), st),
-              "dfn_train_fwd_hier_loss")
-    elif loss is not None:
-        check(lib.dfn_train_fwd_loss(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                     _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c),
-                                     _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                     _ptr(buf.masks[1]), C.byref(loss), st), "dfn_train_fwd_loss")
-    elif buf.n_fine:
-        check(lib.dfn_train_fwd_hier(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                     _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c),
-                                     _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                     _ptr(buf.masks[1]), _ptr(buf.z_all), _ptr(buf.ranks), st), "dfn_train_fwd_hier")
+    # every form takes the same runs of arguments; a form is its entry point and what differs: rays + bounds in front of the
+    # backgrounds or the pixel ids behind them, the hierarchical extras, the loss block
+    net = (buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t)
+    bgs = (_ptr(bg_f32), _ptr(bg_u8))
+    rec = (_ptr(rgb_h), _ptr(rgb_c), _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]), _ptr(buf.masks[1]))
+    hier = (_ptr(buf.z_all), _ptr(buf.ranks)) if buf.n_fine else ()
+    name = _FWD_ENTRY[rays is not None, bool(buf.n_fine), loss is not None and rays is None]
+    if rays is not None:
+        args = (*net, _ptr(rays), _ptr(bounds), *bgs, *rec, *hier)
     else:
-        check(lib.dfn_train_fwd(buf.fwd_tier, C.byref(frame), _ptr(buf.packed[0]), _ptr(buf.packed[1]), _ptr(bias), bias_t,
-                                _ptr(bg_f32), _ptr(bg_u8), _ptr(pix_index), _ptr(rgb_h), _ptr(rgb_c),
-                                _ptr(buf.samples), _ptr(buf.act[0]), _ptr(buf.masks[0]), _ptr(buf.act[1]),
-                                _ptr(buf.masks[1]), st), "dfn_train_fwd")
+        args = (*net, *bgs, _ptr(pix_index), *rec, *hier, *((C.byref(loss),) if loss is not None else ()))
+    check(getattr(lib, name)(*args, st), name)
     ctx.buf, ctx.frame, ctx.bg, ctx.pix = buf, frame, bg, pix_index
     ctx.rays, ctx.bounds = rays, bounds
     # the recorded arrays (and FusedTrainLossFn's d loss / d rgb) live in `buf` and are overwritten by the next forward
@@ -302,21 +291,12 @@ def _fused_backward(ctx, d_h, d_c):
     if not reuse:
         g_flat = _grad_buffer(buf.net, "_g_flat", flat, buf.params)
     zb, zn = (_ptr(g_flat), g_flat.numel()) if reuse else (None, 0)
-    if ctx.rays is not None and buf.n_fine:
-        check(lib.dfn_composite_bwd_hier_rays_z(C.byref(frame), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(bg_f32), _ptr(bg_u8),
-                                                _ptr(buf.samples), _ptr(buf.z_all), _ptr(buf.ranks), _ptr(d_h), _ptr(d_c),
-                                                _ptr(buf.dsamples), zb, zn, st), "dfn_composite_bwd_hier_rays_z")
-    elif ctx.rays is not None:
-        check(lib.dfn_composite_bwd_rays_z(C.byref(frame), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(bg_f32), _ptr(bg_u8),
-                                           _ptr(buf.samples), _ptr(d_h), _ptr(d_c), _ptr(buf.dsamples), zb, zn, st),
-              "dfn_composite_bwd_rays_z")
-    elif buf.n_fine:
-        check(lib.dfn_composite_bwd_hier_z(C.byref(frame), _ptr(ctx.pix), _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples),
-                                           _ptr(buf.z_all), _ptr(buf.ranks), _ptr(d_h), _ptr(d_c), _ptr(buf.dsamples), zb, zn,
-                                           st), "dfn_composite_bwd_hier_z")
-    else:
-        check(lib.dfn_composite_bwd_z(C.byref(frame), _ptr(ctx.pix), _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples),
-                                      _ptr(d_h), _ptr(d_c), _ptr(buf.dsamples), zb, zn, st), "dfn_composite_bwd_z")
+    # one entry point per form (rays or pixel ids, hierarchical or not); what differs is the ray source and the hierarchical extras
+    src = (_ptr(ctx.rays), _ptr(ctx.bounds)) if ctx.rays is not None else (_ptr(ctx.pix),)
+    hier = (_ptr(buf.z_all), _ptr(buf.ranks)) if buf.n_fine else ()
+    name = _BWD_ENTRY[ctx.rays is not None, bool(buf.n_fine)]
+    check(getattr(lib, name)(C.byref(frame), *src, _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples), *hier, _ptr(d_h), _ptr(d_c),
+                             _ptr(buf.dsamples), zb, zn, st), name)
     g_bias = torch.empty(buf.nb[0] + buf.nb[1], dtype=torch.float32, device=dev)
     main = torch.cuda.current_stream(dev)
     # (with more than one rank RCCL brings a fifth stream; the package asks the runtime for eight hardware queues then

@@ -1,38 +1,14 @@
 # render_variants.sh - the render variants of libdfanerf.so, for the build: sourced by build.sh and tools/build_variant.sh.
-# One line per variant: the object dfn_render_<name>.o is csrc/dfn_render_variant.hip (its header describes the scheme) compiled
-# with DFN_VARIANT_TIER = <tier> and DFN_VARIANT_FLAGS = <flags>.  The library's side of the list is the dispatch table of
-# csrc/dfn_render.hip; an entry there without a line here does not link.
-RENDER_VARIANTS="
-f32             TIER_F32    0
-bf16            TIER_BF16   0
-bf16e           TIER_BF16   TIER_E4M3
-f16             TIER_F16    0
-f16x3           TIER_F16X3  0
-f32_w128        TIER_F32    TIER_W128
-f16_w128        TIER_F16    TIER_W128
-f16x3_w128      TIER_F16X3  TIER_W128
-f32_aux         TIER_F32    TIER_AUX
-f16_aux         TIER_F16    TIER_AUX
-f16x3_aux       TIER_F16X3  TIER_AUX
-f32_w128_aux    TIER_F32    TIER_W128|TIER_AUX
-f16_w128_aux    TIER_F16    TIER_W128|TIER_AUX
-f16x3_w128_aux  TIER_F16X3  TIER_W128|TIER_AUX
-f32_rays        TIER_F32    TIER_RAYS
-f16_rays        TIER_F16    TIER_RAYS
-f16x3_rays      TIER_F16X3  TIER_RAYS
-f32_w128_rays   TIER_F32    TIER_W128|TIER_RAYS
-f16_w128_rays   TIER_F16    TIER_W128|TIER_RAYS
-f16x3_w128_rays TIER_F16X3  TIER_W128|TIER_RAYS
-f32_z           TIER_F32    TIER_ZVALS
-f16_z           TIER_F16    TIER_ZVALS
-f16x3_z         TIER_F16X3  TIER_ZVALS
-f32_w128_z      TIER_F32    TIER_W128|TIER_ZVALS
-f16_w128_z      TIER_F16    TIER_W128|TIER_ZVALS
-f16x3_w128_z    TIER_F16X3  TIER_W128|TIER_ZVALS
-f32_rays_train  TIER_F32    TIER_RAYS|TIER_TRAIN
-bf16_rays_train TIER_BF16   TIER_RAYS|TIER_TRAIN
-bf16e_rays_train TIER_BF16  TIER_RAYS|TIER_TRAIN|TIER_E4M3
-"
+# The list is csrc/dfn_render_variants.h (DFN_VARIANT(name, tier, flags), one per line; that file says what the flags mean) and is
+# read from there: the object dfn_render_<name>.o is csrc/dfn_render_variant.hip compiled with DFN_VARIANT_TIER = <tier> and
+# DFN_VARIANT_FLAGS = <flags>.  The library's dispatch table (csrc/dfn_render.hip) is generated from the same lines.
+VARIANT_LIST="$(dirname "${BASH_SOURCE[0]}")/csrc/dfn_render_variants.h"
+RENDER_VARIANTS="$(sed -n 's/^DFN_VARIANT(\([a-z0-9_]*\), *\(TIER_[A-Z0-9]*\), *\([A-Z0-9_| ]*\))$/\1 \2 \3/p' "$VARIANT_LIST" | sed 's/ *| */|/g')"
+# a list line this pattern does not take (upper case in the name, something behind the closing bracket) must not drop out of the build
+if [ "$(grep -c '^DFN_VARIANT' "$VARIANT_LIST")" != "$(grep -c . <<< "$RENDER_VARIANTS")" ]; then
+  echo "render_variants.sh: a DFN_VARIANT line of $VARIANT_LIST is not of the form DFN_VARIANT(name, TIER_X, FLAGS)" >&2
+  return 1 2>/dev/null || exit 1
+fi
 # variant_units [tier ...]: the unit names (dfn_render_<name>) of the variants of these tiers, or of all of them
 variant_units() {
   local n t f
