@@ -204,8 +204,11 @@ DFN_DEV void stream_begin(Stream& s, lds_char* ring, int wave, int lane) {
 // (into the slot slab g-1 releases here) is NOT issued here: a burst of 32 loads per CU right behind the barrier
 // keeps the vector-memory issue path busy for ~500 cycles during which no wave can issue an MFMA (in-order
 // issue).  Its pieces are spread over the fragment reads of slab g instead (Fetch::load).
+// first: the first hand-over of a pass (Fetch::prime).  f16 tier, the lane's read address (LABNOTES.md 4.8): the first hand-over of a
+// pass computes it from the lane id, every other one adds the wave-uniform distance to the next ring slot (one vector add; the
+// register is dead between passes).  The other tiers ignore `first`.
 template <int TIER>
-DFN_DEV void slab_advance(Stream& s, lds_char* ring, int wave, int lane) {
+DFN_DEV void slab_advance(Stream& s, lds_char* ring, int wave, int lane, bool first) {
     using C = TierCfg<TIER>;
     // my share of slab g has landed (only slab g+1's pieces are younger), and my fragment reads of slab g-1 have
     // returned (its slot is refilled during slab g; the compiler knows nothing about that hazard)
@@ -229,11 +232,15 @@ DFN_DEV void slab_advance(Stream& s, lds_char* ring, int wave, int lane) {
     s.rd_slot = (s.rd_slot + 1 == RING_SLOTS) ? 0u : s.rd_slot + 1;
     s.rd_off = s.rd_slot * SLAB_BYTES;
     if constexpr (tier_m16(TIER)) {
-        // (computed from the lane id at every hand-over, behind an opaque copy: hoisted out of the pass loop the offset and its
-        // G = 1 form are two more registers that live through the whole kernel, which has none to spare)
-        int l = lane;
-        asm volatile("" : "+v"(l));
-        s.rd_vaddr = (unsigned)(unsigned long)ring + m16_lane_off(l, 2) + s.rd_off;
+        // (computed from the lane id behind an opaque copy, at the first hand-over of every pass: hoisted out of the pass loop the
+        // offset and its G = 1 form are two more registers that live through the whole kernel, which has none to spare)
+        if (!first) {
+            s.rd_vaddr += (s.rd_slot == 0) ? 0u - (unsigned)((RING_SLOTS - 1) * SLAB_BYTES) : (unsigned)SLAB_BYTES;
+        } else {
+            int l = lane;
+            asm volatile("" : "+v"(l));
+            s.rd_vaddr = (unsigned)(unsigned long)ring + m16_lane_off(l, 2) + s.rd_off;
+        }
     } else s.rd_vaddr = (unsigned)(unsigned long)ring + (unsigned)lane * 16u + s.rd_off;
     s.pf_owed += C::LOADS_PER_SLAB;
 }
@@ -619,6 +626,29 @@ DFN_DEV void frag_read16(u32x4& dst, unsigned vaddr, int code) {
     }
 }
 #undef DFN_FRAG_CASE
+// the same read as a REFILL of a ring slot ("+v"): the new fragment takes the registers of the one the slot held, behind that one's
+// MFMAs - the ring stays PF_DEPTH register quads (left to the allocator, "=v" fragments were renamed over up to nine quads)
+#define DFN_FRAG_CASE(K)                                                                                      \
+    case 2 * (K):                                                                                             \
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(vaddr), "n"((K) * FRAG_BYTES) : "memory"); \
+        break;                                                                                                \
+    case 2 * (K) + 1:                                                                                         \
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst) : "v"(vaddr), "n"((K) * FRAG_BYTES + M16_T_BYTES) : "memory"); \
+        break;
+DFN_DEV void frag_refill16(u32x4& dst, unsigned vaddr, int code) {
+    switch (code) {
+        DFN_FRAG_CASE(0) DFN_FRAG_CASE(1) DFN_FRAG_CASE(2) DFN_FRAG_CASE(3) DFN_FRAG_CASE(4) DFN_FRAG_CASE(5)
+        DFN_FRAG_CASE(6) DFN_FRAG_CASE(7) DFN_FRAG_CASE(8) DFN_FRAG_CASE(9) DFN_FRAG_CASE(10) DFN_FRAG_CASE(11)
+        DFN_FRAG_CASE(12) DFN_FRAG_CASE(13) DFN_FRAG_CASE(14) DFN_FRAG_CASE(15) DFN_FRAG_CASE(16) DFN_FRAG_CASE(17)
+        DFN_FRAG_CASE(18) DFN_FRAG_CASE(19) DFN_FRAG_CASE(20) DFN_FRAG_CASE(21) DFN_FRAG_CASE(22) DFN_FRAG_CASE(23)
+        DFN_FRAG_CASE(24) DFN_FRAG_CASE(25) DFN_FRAG_CASE(26) DFN_FRAG_CASE(27) DFN_FRAG_CASE(28) DFN_FRAG_CASE(29)
+        DFN_FRAG_CASE(30) DFN_FRAG_CASE(31)
+        default: __builtin_unreachable();
+    }
+}
+#undef DFN_FRAG_CASE
+// (The registers the in-place refill frees are what lets the paired wait below and the stepped read address of slab_advance fit 256
+// registers without scratch: each of the two alone, on "=v" refills, spills - LABNOTES.md 4.8)
 // wait until at most `younger` LDS operations issued after the read of `r` are outstanding (they return in order); the
 // "+v" ties the wait to the register so that the MFMA consuming it cannot be scheduled above it
 DFN_DEV void frag_wait(u32x4& r, int younger) {
@@ -631,6 +661,17 @@ DFN_DEV void frag_wait(u32x4& r, int younger) {
         case 5: asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(r)); break;
         case 6: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(r)); break;
         default: asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(r)); break;
+    }
+}
+// f16 tier (LABNOTES.md 4.8): the same wait for the two reads (T0, T1) of a tile at once (r0 the older), both tied to it, in front of
+// their four MFMAs.  hipcc treats every register an asm statement defines as a possible dst_sel-forwarding result: a vector
+// instruction that reads it needs one wait state behind the statement, and asm statements count as none - `s_waitcnt ; s_nop 0 ;
+// v_mfma` wherever a wait sits right in front of its MFMAs.  Per tile that is half the waits and the pad once, not twice.
+DFN_DEV void frag_wait2(u32x4& r0, u32x4& r1, int younger) {
+    switch (younger) {
+        case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0), "+v"(r1)); break;
+        case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r0), "+v"(r1)); break;
+        default: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r0), "+v"(r1)); break;
     }
 }
 static_assert(PF_DEPTH >= 1 && PF_DEPTH <= 8, "frag_wait covers up to 7 younger reads");
@@ -654,11 +695,13 @@ template <int TIER> struct Fetch {
     // fragments 4 q .. 4 q + 3 ([k-unit][tile]: k-groups 0, 1 read k-unit 2 v, k-groups 2, 3 k-unit 2 v + 1); reads 2 q, 2 q + 1 of a
     // G = 1 group are T0, T1 of fragments 2 q, 2 q + 1.  One read per fragment, in stream order: slab hand-over, ring and the
     // spreading of the LDS-DMA pieces are those of the other tiers.
-    template <class CT, class H> DFN_DEV void load(int slot, int fp, Stream& s, const CT& c, H&& hook, int gl = 2) {
+    // first: the first read of a pass - only prime() says true; every other read of a pass steps the f16 tier's read address from
+    // the one the pass's first hand-over computed (slab_advance)
+    template <class CT, class H> DFN_DEV void load(int slot, int fp, Stream& s, const CT& c, H&& hook, int gl = 2, bool first = false) {
         using C = TierCfg<TIER>;
         constexpr int GAP = SLAB_FRAGS / C::LOADS_PER_SLAB;       // fragment reads between two DMA pieces
         if (fp % SLAB_FRAGS == 0) {
-            slab_advance<TIER>(s, c.ring, c.wave, c.lane);
+            slab_advance<TIER>(s, c.ring, c.wave, c.lane, first);
             hook();
         }
         if constexpr (tier_m16(TIER)) {
@@ -670,7 +713,10 @@ template <int TIER> struct Fetch {
                 asm volatile("" : "+v"(l));
                 vaddr -= (l >> 5) << 10;
             }
-            if constexpr (use_asm_fetch<TIER, CT>()) frag_read16(buf[slot], vaddr, 2 * (off / FRAG_BYTES) + (off % FRAG_BYTES != 0));
+            if constexpr (use_asm_fetch<TIER, CT>()) {
+                if (fp >= PF_DEPTH) frag_refill16(buf[slot], vaddr, 2 * (off / FRAG_BYTES) + (off % FRAG_BYTES != 0));
+                else frag_read16(buf[slot], vaddr, 2 * (off / FRAG_BYTES) + (off % FRAG_BYTES != 0));
+            }
             else buf[slot] = *(const lds_u32x4*)(c.ring + m16_lane_off(c.lane, gl) + s.rd_off + off);
         } else if constexpr (use_asm_fetch<TIER, CT>()) frag_read(buf[slot], s.rd_vaddr, fp % SLAB_FRAGS);
         else buf[slot] = *(const lds_u32x4*)(c.ring + c.lane * 16 + s.rd_off + (fp % SLAB_FRAGS) * FRAG_BYTES);
@@ -692,7 +738,7 @@ template <int TIER> struct Fetch {
         stream_flush<TIER, use_asm_dma<TIER, CT>()>(s, c.ring, c.wave, c.lane);
         stream_pass_begin(s);
 #pragma unroll
-        for (int i = 0; i < PF_DEPTH; ++i) load(i, i, s, c);
+        for (int i = 0; i < PF_DEPTH; ++i) load(i, i, s, c, NoHook{}, 2, i == 0);
     }
 };
 
@@ -723,7 +769,8 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
                     const int left = (KU / 2 - v) * 2 * G - 2 * g - T - 1;      // reads after this one in the group
                     if constexpr (ASM) {
                         const int after = (TAIL < 0) ? PF_DEPTH : left + TAIL;             // ... in the pass
-                        frag_wait(fe.buf[f % PF_DEPTH], after < PF_DEPTH - 1 ? after : PF_DEPTH - 1);
+                        // T0 waits for T1's read too (the next one: at most reads f + 2, f + 3 of the pass stay in flight)
+                        if (T == 0) frag_wait2(fe.buf[f % PF_DEPTH], fe.buf[(f + 1) % PF_DEPTH], after - 1 < PF_DEPTH - 2 ? after - 1 : PF_DEPTH - 2);
                     }
                     const f16x8 a = __builtin_bit_cast(f16x8, fe.buf[f % PF_DEPTH]);
                     if constexpr (!ASM) {

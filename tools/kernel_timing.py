@@ -33,8 +33,12 @@ z = out[-1].cpu().numpy()[:, 64:72].astype(np.float64)
 tot, real, mlp, pdf, wait, bar, issue, wave = z.T
 print(f"rays {len(tot)}  clock = {np.mean(tot / real) * 100:.0f} MHz (shader cycles per 100 MHz tick)")
 npass = 6 * fields        # 2 coarse + 4 fine tiles per field
+# MFMA pipe cycles of a pass: 32 per 32x32x16 MFMA (head 1138, torso 1302 fragments); the f16 tier runs two 16-cycle 16x16x32 MFMAs
+# per fragment, less the 34 dead T1 MFMAs of the thin sigma / colour tiles: 2242 MFMAs in the head pass (LABNOTES.md 4.7)
+tier = sys.argv[2] if len(sys.argv) > 2 else "f16"
+ideal = 2 * 16 * 2242 if (tier == "f16" and fields == 1) else 2 * 32 * (1138 if fields == 1 else (1138 + 1302) / 2)
 print(f"per ray: total {tot.mean():.0f} cyc | mlp {mlp.mean():.0f} ({mlp.mean()/tot.mean():.1%}) = {mlp.mean()/npass:.0f} per pass"
-      f" (ideal MFMA-only, 2 waves/SIMD: {2*32*(1138 if fields==1 else (1138+1302)/2):.0f}) | pdf+merge {pdf.mean():.0f} ({pdf.mean()/tot.mean():.1%})")
+      f" (ideal MFMA-only, 2 waves/SIMD: {ideal:.0f}) | pdf+merge {pdf.mean():.0f} ({pdf.mean()/tot.mean():.1%})")
 print(f"slab hand-over per ray: waitcnt {wait.mean():.0f} ({wait.mean()/tot.mean():.1%})  barrier {bar.mean():.0f} ({bar.mean()/tot.mean():.1%})"
       f"  dma issue {issue.mean():.0f} ({issue.mean()/tot.mean():.1%})")
 for w in range(8):

@@ -15,11 +15,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = {
-    "c2": ["--workload", "c2"], "c1": ["--workload", "c1"], "c3": ["--workload", "c3"], "c5": ["--workload", "c5"],
-    "c2_512": ["--workload", "c2", "--size", "512"],
-    "c2_f32": ["--workload", "c2", "--tier", "f32"], "c2_bf16": ["--workload", "c2", "--tier", "bf16"], "c4": ["--workload", "c4"],
-}
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from lib_ab import CASES, run_bench                 # noqa: E402  (the workload table and the bench.py runner, shared)
+
 CHANGED = ("c2", "c1", "c3", "c5", "c2_512")
 
 ap = argparse.ArgumentParser()
@@ -42,19 +40,10 @@ def say(s):
 
 
 def bench(case, lib):
-    env = dict(os.environ)
-    env.pop("DFN_LIB", None)
-    if lib:
-        env["DFN_LIB"] = lib
-    steps = a.steps if case != "c5" else max(2, a.steps // 8)         # (a c5 step is eight frames)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(a.warmup)] + CASES[case]
-    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
-    js = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-    if out.returncode != 0 or len(js) != 1:
-        sys.exit(f"mfma16_ab: bench.py failed for {case}:\n{out.stdout[-2000:]}{out.stderr[-4000:]}")
-    r = json.loads(js[0])
-    rf = r.get("roofline") or {}
-    return {"ms": r["ms_per_step"], "kernel_ms": rf.get("kernel_ms"), "ghz": rf.get("clock_ghz")}
+    try:
+        return run_bench(case, lib, a.steps, a.warmup)
+    except RuntimeError as e:
+        sys.exit(f"mfma16_ab: {e}")
 
 
 say(f"mfma16_ab: in-tree library against {os.path.basename(parent)}; bench.py --gpus 1 --steps {a.steps} --warmup {a.warmup}, one process per "
