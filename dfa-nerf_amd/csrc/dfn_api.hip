@@ -367,6 +367,35 @@ int dfn_adam_multi(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int 
                                       (hipStream_t)stream), "adam_multi_kernel");
 }
 
+long dfn_grad_stats_floats(long n_chunks) {
+    if (n_chunks <= 0 || n_chunks > INT_MAX) return fail(DFN_E_ARG, "dfn_grad_stats_floats: n_chunks must be in 1 .. 2^31 - 1");
+    return 2 * n_chunks;
+}
+
+int dfn_grad_stats(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int n_chunks, long chunk_base, int finish,
+                   float max_norm, int skip_nonfinite, float* workspace, DfnGradStats* stats_dev, void* stream) {
+    if (!items_dev || !chunks_dev) return fail(DFN_E_ARG, "dfn_grad_stats: items / chunks table is NULL");
+    if (n_chunks <= 0) return fail(DFN_E_ARG, "dfn_grad_stats: n_chunks must be positive");
+    if (chunk_base < 0 || chunk_base > INT_MAX - n_chunks) return fail(DFN_E_ARG, "dfn_grad_stats: bad chunk_base");
+    if (!stats_dev) return fail(DFN_E_ARG, "dfn_grad_stats: the stats record is NULL");
+    if (!workspace) return fail(DFN_E_ARG, "dfn_grad_stats: the workspace is NULL (dfn_grad_stats_floats)");
+    if (max_norm != max_norm) return fail(DFN_E_ARG, "dfn_grad_stats: max_norm is NaN");
+    return launched(launch_grad_stats(items_dev, chunks_dev, n_chunks, chunk_base, finish != 0, max_norm, skip_nonfinite,
+                                      workspace, stats_dev, (hipStream_t)stream), "grad_stats_kernel");
+}
+
+int dfn_adam_multi_guarded(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int n_chunks, float lr, double beta1,
+                           double beta2, float eps, float bias_c1, float bias_c2_sqrt, long t_host,
+                           const DfnGradStats* stats_dev, void* stream) {
+    if (!items_dev || !chunks_dev) return fail(DFN_E_ARG, "dfn_adam_multi_guarded: items / chunks table is NULL");
+    if (n_chunks <= 0) return fail(DFN_E_ARG, "dfn_adam_multi_guarded: n_chunks must be positive");
+    if (!stats_dev) return fail(DFN_E_ARG, "dfn_adam_multi_guarded: the stats record is NULL (dfn_grad_stats fills it)");
+    if (!(bias_c1 > 0.f) || !(bias_c2_sqrt > 0.f) || t_host < 1)
+        return fail(DFN_E_ARG, "dfn_adam_multi_guarded: bias corrections must be positive and t_host >= 1");
+    return launched(launch_adam_multi_guarded(items_dev, chunks_dev, n_chunks, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt,
+                                              t_host, stats_dev, (hipStream_t)stream), "adam_multi_guarded_kernel");
+}
+
 // The host-side requests of the fused launches: what an entry point was asked for, by name.  Each entry point fills one (value-
 // initialised: every member it does not name is null / 0 = off) and states the variant flags of its form (dfn_render_variants.h).
 // `who`: the name the shared checks report under - the texts callers match on.

@@ -43,4 +43,9 @@ hipError_t launch_mfma_probe(float* out, hipStream_t st);
 hipError_t launch_mfma16_probe(float* out, hipStream_t st);
 hipError_t launch_adam_multi(const DfnAdamItem* items, const void* chunks, int n_chunks, float lr, double beta1, double beta2,
                              float eps, float bias_c1, float bias_c2_sqrt, hipStream_t st);
+hipError_t launch_grad_stats(const DfnAdamItem* items, const void* chunks, int n_chunks, long chunk_base, bool finish,
+                             float max_norm, int skip_nonfinite, float* workspace, DfnGradStats* stats, hipStream_t st);
+hipError_t launch_adam_multi_guarded(const DfnAdamItem* items, const void* chunks, int n_chunks, float lr, double beta1,
+                                     double beta2, float eps, float bias_c1, float bias_c2_sqrt, long t_host,
+                                     const DfnGradStats* stats, hipStream_t st);
 }  // namespace dfn

@@ -899,4 +899,129 @@ hipError_t launch_adam_multi(const DfnAdamItem* items, const void* chunks, int n
     return hipGetLastError();
 }
 
+// ---- gradient guard in front of the Adam launch (include/dfanerf.h: dfn_grad_stats, dfn_adam_multi_guarded) ----------
+// The same tables as above.  Per chunk an f32 sum of <= 2048 squares in a fixed order (8 per thread pairwise in index order, a
+// butterfly over the 256 threads) and an integer count of non-finite elements; a one-block pass adds the partials in index
+// order in double and takes the step's decision.  No floating-point atomics: the result does not depend on block order.
+// A gradient is only ever an operand here (never an index or a bound): a NaN in the buffer is an ordinary float.
+__device__ __forceinline__ bool f32_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__global__ __launch_bounds__(256) void grad_stats_chunk_kernel(const DfnAdamItem* items, const int2* chunks, float* partials) {
+    const int2 ch = chunks[blockIdx.x];
+    const DfnAdamItem it = items[ch.x];
+    const long i0 = (long)ch.y * DFN_ADAM_CHUNK;
+    const long i1 = (i0 + DFN_ADAM_CHUNK < it.n) ? i0 + DFN_ADAM_CHUNK : it.n;
+    float q[8];
+    int bad = 0;
+    for (int j = 0; j < 8; ++j) {
+        const long i = i0 + threadIdx.x + 256 * j;
+        const float g = (i < i1) ? it.grad[i] : 0.f;
+        bad += f32_nonfinite(g) ? 1 : 0;
+        q[j] = g * g;
+    }
+    float s = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+    for (int d = 1; d < 64; d <<= 1) {                      // within the wave: every lane ends with the same bits
+        s = s + __shfl_xor(s, d, 64);
+        bad += __shfl_xor(bad, d, 64);
+    }
+    __shared__ float ws[4];
+    __shared__ int wb[4];
+    if ((threadIdx.x & 63) == 0) {
+        ws[threadIdx.x >> 6] = s;
+        wb[threadIdx.x >> 6] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                 // d = 64, 128 of the butterfly
+        partials[2 * (long)blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+        ((int*)partials)[2 * (long)blockIdx.x + 1] = wb[0] + wb[1] + wb[2] + wb[3];
+    }
+}
+__global__ __launch_bounds__(256) void grad_stats_finish_kernel(const float* partials, long n, float max_norm, int skip_nonfinite,
+                                                                 DfnGradStats* st) {
+    __shared__ float tile[512];
+    __shared__ int bad_all;
+    if (threadIdx.x == 0) bad_all = 0;
+    __syncthreads();
+    double sumsq = 0.0;                                      // thread 0's: the partials in index order
+    int bad = 0;
+    for (long base = 0; base < n; base += 512) {
+        const int m = (n - base < 512) ? (int)(n - base) : 512;
+        for (int k = threadIdx.x; k < m; k += 256) {
+            tile[k] = partials[2 * (base + k)];
+            bad += ((const int*)partials)[2 * (base + k) + 1];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < m; ++k) sumsq += (double)tile[k];
+        __syncthreads();
+    }
+    if (bad) atomicAdd(&bad_all, bad);                       // integers: any order gives the same count
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool finite = isfinite(sumsq);
+        int nonfinite = bad_all;
+        if (!finite && nonfinite == 0) nonfinite = 1;        // finite elements whose squares overflowed the f32 partial
+        const float norm = (float)sqrt(sumsq);
+        float coef = 1.0f;
+        if (max_norm > 0.f) {
+            const float c = max_norm / (norm + 1e-6f);
+            coef = (c < 1.0f) ? c : 1.0f;
+        }
+        const int skip = (skip_nonfinite && (nonfinite > 0 || !finite)) ? 1 : 0;
+        st->sumsq = sumsq;
+        st->norm = norm;
+        st->nonfinite = nonfinite;
+        st->clip_coef = coef;
+        st->skip = skip;
+        st->skipped_total += skip;
+    }
+}
+hipError_t launch_grad_stats(const DfnAdamItem* items, const void* chunks, int n_chunks, long chunk_base, bool finish,
+                             float max_norm, int skip_nonfinite, float* workspace, DfnGradStats* stats, hipStream_t st) {
+    hipLaunchKernelGGL(grad_stats_chunk_kernel, dim3(n_chunks), dim3(256), 0, st, items, (const int2*)chunks,
+                       workspace + 2 * chunk_base);
+    if (finish)
+        hipLaunchKernelGGL(grad_stats_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, chunk_base + n_chunks,
+                           max_norm, skip_nonfinite, stats);
+    return hipGetLastError();
+}
+
+// adam_multi_kernel behind the guard: nothing is written on a skip, g = grad * clip_coef otherwise (clip_coef == 1.0f: the same
+// bits).  A skipped step does not count: t_eff = t_host - skipped_total; with no skip so far the host's bias corrections are
+// used as passed (bit-identical to adam_multi_kernel), otherwise they are recomputed here in double.
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const DfnAdamItem* items, const int2* chunks, float lr, float beta2,
+                                                                  float om_beta1, float om_beta2, float eps, float bias_c1,
+                                                                  float bias_c2_sqrt, double beta1_d, double beta2_d, long t_host,
+                                                                  const DfnGradStats* st) {
+    if (st->skip) return;
+    const float coef = st->clip_coef;
+    const int skipped = st->skipped_total;
+    if (skipped != 0) {
+        const double t_eff = (double)(t_host - skipped);
+        bias_c1 = (float)(1.0 - pow(beta1_d, t_eff));
+        bias_c2_sqrt = (float)sqrt(1.0 - pow(beta2_d, t_eff));
+    }
+    const int2 ch = chunks[blockIdx.x];
+    const DfnAdamItem it = items[ch.x];
+    const long i0 = (long)ch.y * DFN_ADAM_CHUNK;
+    const long i1 = (i0 + DFN_ADAM_CHUNK < it.n) ? i0 + DFN_ADAM_CHUNK : it.n;
+    const float step_size = lr / bias_c1;
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+        const float g = it.grad[i] * coef;
+        float m = it.exp_avg[i], v = it.exp_avg_sq[i];
+        m = m + (g - m) * om_beta1;
+        v = beta2 * v + om_beta2 * g * g;
+        const float denom = sqrtf(v) / bias_c2_sqrt + eps;
+        it.param[i] -= step_size * m / denom;
+        it.exp_avg[i] = m;
+        it.exp_avg_sq[i] = v;
+    }
+}
+hipError_t launch_adam_multi_guarded(const DfnAdamItem* items, const void* chunks, int n_chunks, float lr, double beta1,
+                                     double beta2, float eps, float bias_c1, float bias_c2_sqrt, long t_host,
+                                     const DfnGradStats* stats, hipStream_t st) {
+    hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3(n_chunks), dim3(256), 0, st, items, (const int2*)chunks, lr, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_c1, bias_c2_sqrt, beta1, beta2, t_host, stats);
+    return hipGetLastError();
+}
+
 }  // namespace dfn

@@ -36,6 +36,11 @@ class DfnTrainLoss(C.Structure):
                 ("losses", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class DfnGradStats(C.Structure):        # include/dfanerf.h: 32 bytes of device memory, filled by dfn_grad_stats
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("nonfinite", C.c_int32), ("clip_coef", C.c_float),
+                ("skip", C.c_int32), ("skipped_total", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DfnError(RuntimeError):
     pass
 
@@ -67,6 +72,11 @@ def _load():
         "dfn_fold_bias": (i32, [i32, i32, fp, fp, fp, fp, fp, vp]),
         "dfn_fold_bias_bwd": (i32, [i32, i32, fp, fp, fp, fp, fp, fp, fp, vp]),
         "dfn_adam_multi": (i32, [vp, vp, i32, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, vp]),
+        # the gradient guard in front of it (optim.HipAdam: max_grad_norm / skip_nonfinite)
+        "dfn_grad_stats_floats": (lg, [lg]),
+        "dfn_grad_stats": (i32, [vp, vp, i32, lg, i32, C.c_float, i32, fp, vp, vp]),
+        "dfn_adam_multi_guarded": (i32, [vp, vp, i32, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, C.c_float, lg, vp,
+                                         vp]),
         "dfn_render_fwd": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, fp, fp, vp]),
         "dfn_render_fwd_u8": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, vp, vp, vp]),
         "dfn_render_fwd_aux": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, fp, vp]),

@@ -7,14 +7,20 @@ its step takes 104 us on an MI355X, the five optimizers of a training step 250 u
 torch.optim.Adam(fused=True) (state[p] = {"step": 0-dim f32 device tensor, "exp_avg", "exp_avg_sq"}), so checkpoints
 move freely between the two; parameters of one group at different step counts (a resumed reference checkpoint has no
 state for the parameters its autograd never reached) are stepped in one launch per distinct count; anything this class
-does not cover (weight decay, amsgrad, maximize, non-f32 or non-contiguous tensors) goes through torch's own step()."""
+does not cover (weight decay, amsgrad, maximize, non-f32 or non-contiguous tensors) goes through torch's own step().
+
+The gradient guard (max_grad_norm / skip_nonfinite, both off by default; include/dfanerf.h: dfn_grad_stats,
+dfn_adam_multi_guarded): the total norm of the step's gradients over ALL its launch tables, torch.nn.utils.clip_grad_norm_'s
+coefficient and AMP's "a step with a non-finite gradient is not applied", on the device, on the stream the step uses, in a
+fixed summation order and without host synchronisation.  The gradient tensors are only read - the clip scales the value the
+update uses, not the buffer (training._FlatNet hands the same views out every step and other streams may still read them)."""
 import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, DfnGradStats
 
 ADAM_CHUNK = 2048          # DFN_ADAM_CHUNK in include/dfanerf.h
 
@@ -32,19 +38,75 @@ def _bump_versions(tensors):
 
 
 class HipAdam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or \
+                    not math.isfinite(max_grad_norm) or max_grad_norm < 0:
+                raise ValueError(f"HipAdam: max_grad_norm must be a finite number >= 0 or None (no clipping), got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
         super().__init__(params, lr=lr, betas=betas, eps=eps, fused=True)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self._guarded = max_grad_norm is not None or self.skip_nonfinite
+        # the guard's device memory: {"rec": int32 [8] = one DfnGradStats, "ws": f32 workspace, "n": its chunks}, made when
+        # a launch table is built; _skipped_base: skips of records folded into the host's counts since (see _fold_skips)
+        self._gs, self._skipped_base = None, 0
         # group index -> {"pkey", "gkey", "buckets": [{"ps", "t", "items", "chunks", "n_chunks", "host"}]}: one bucket
         # (= one launch) per distinct step count of the group's parameters
         self._cache = {}
 
     # ---- state bookkeeping: torch keeps a step counter per parameter, a launch needs one per bucket ---------------
     def _sync_steps(self):
+        k = self._read_stats()["skipped_total"] if self._gs is not None else 0     # (guard: skipped steps do not count)
         for c in self._cache.values():
             for b in c["buckets"]:
                 steps = [self.state[p]["step"] for p in b["ps"]]
                 torch._foreach_zero_(steps)
-                torch._foreach_add_(steps, float(b["t"]))
+                torch._foreach_add_(steps, float(b["t"] - k))
+
+    # ---- the guard's record ----------------------------------------------------------------------------------------
+    def _read_stats(self):
+        """The device record as a dict (one 32-byte device-to-host copy behind the stream the step ran on)."""
+        s = getattr(self, "dfn_stream", None)
+        if s is not None:
+            s.synchronize()
+        r = DfnGradStats.from_buffer_copy(self._gs["rec"].cpu().numpy().tobytes())
+        return {"sumsq": r.sumsq, "norm": r.norm, "nonfinite": r.nonfinite, "clip_coef": r.clip_coef, "skip": r.skip,
+                "skipped_total": r.skipped_total}
+
+    def grad_stats(self):
+        """{"norm", "nonfinite", "clip_coef", "skipped_total"} of the last step (guard on).  The one place the guard waits for
+        the device.  skipped_total counts since construction / load_state_dict."""
+        if not self._guarded:
+            raise ValueError("HipAdam.grad_stats: the gradient guard is off (max_grad_norm=None, skip_nonfinite=False)")
+        if self._gs is None:
+            return {"norm": 0.0, "nonfinite": 0, "clip_coef": 1.0, "skipped_total": self._skipped_base}
+        r = self._read_stats()
+        return {"norm": r["norm"], "nonfinite": r["nonfinite"], "clip_coef": r["clip_coef"],
+                "skipped_total": self._skipped_base + r["skipped_total"]}
+
+    def _fold_skips(self):
+        """Before a table is rebuilt: take the record's skip count off every bucket's launch count (the kernel's
+        t_eff = t - skipped_total) and drop the record - the next one starts at skipped_total = 0."""
+        if self._gs is None:
+            return
+        k = self._read_stats()["skipped_total"]
+        for c in self._cache.values():
+            for b in c["buckets"]:
+                b["t"] -= k
+        self._skipped_base += k
+        self._gs = None
+
+    def _guard_memory(self, dev, n_chunks):
+        """The record and the workspace: made in the step that builds a launch table (_build drops them), kept until the next."""
+        gs = self._gs
+        if gs is not None and gs["n"] >= n_chunks:
+            return gs
+        if gs is None:
+            gs = self._gs = {"rec": torch.zeros(8, dtype=torch.int32, device=dev), "ws": None, "n": 0}
+        n = check(lib.dfn_grad_stats_floats(n_chunks), "dfn_grad_stats_floats")
+        gs["ws"], gs["n"] = torch.empty(n, dtype=torch.float32, device=dev), n_chunks
+        torch.cuda.current_stream(dev).synchronize()      # made on the current stream, used on the step's
+        return gs
 
     def state_dict(self):
         self._sync_steps()
@@ -53,13 +115,19 @@ class HipAdam(torch.optim.Adam):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._cache.clear()
+        self._gs, self._skipped_base = None, 0
 
     def _torch_step(self, closure):
+        if self._guarded:
+            raise ValueError("HipAdam: max_grad_norm / skip_nonfinite guard the dfn_adam_multi path only, and this configuration "
+                             "(weight decay, amsgrad, maximize, a tensor lr, a non-f32 or non-contiguous tensor) goes through "
+                             "torch.optim.Adam.step(): it would run unguarded.  Construct the optimizer without the guard")
         self._sync_steps()
         self._cache.clear()
         return super().step(closure)
 
     def _build(self, gi, ps, pkey, gkey):
+        self._fold_skips()
         old = self._cache.get(gi)
         if old is not None and old["pkey"] == pkey:
             # same parameters, new gradient buffers: the counts carry on
@@ -182,6 +250,8 @@ class HipAdam(torch.optim.Adam):
             elif not c["ps"]:
                 continue
             plans.append((group, c))
+        if self._guarded:
+            return self._guarded_launches(plans, stream, loss)
         for group, c in plans:
             b1, b2 = group["betas"]
             for b in c["buckets"]:
@@ -196,6 +266,35 @@ class HipAdam(torch.optim.Adam):
                 # would, or everything keyed on them (Decoder.packed()'s repack-on-change, autograd's saved-tensor
                 # checks) goes stale
                 _bump_versions(b["ps"])
+        return loss
+
+    def _guarded_launches(self, plans, stream, loss):
+        """The step with the guard on: dfn_grad_stats over every table (one norm; the finishing pass behind the last one),
+        then the guarded Adam launches - all on the stream the plain step would use, so with several ranks behind
+        parallel.StepReducer's all-reduce like the update itself: every rank decides on the same averaged bits."""
+        tables = [(group, b) for group, c in plans for b in c["buckets"]]
+        if not tables:
+            return loss
+        dev = tables[0][1]["ps"][0].device
+        cs = stream if stream is not None else torch.cuda.current_stream(dev)
+        gs = self._guard_memory(dev, sum(b["n_chunks"] for _, b in tables))
+        rec, ws, st = C.c_void_p(gs["rec"].data_ptr()), C.c_void_p(gs["ws"].data_ptr()), C.c_void_p(cs.cuda_stream)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        base = 0
+        for k, (group, b) in enumerate(tables):
+            check(lib.dfn_grad_stats(C.c_void_p(b["items"].data_ptr()), C.c_void_p(b["chunks"].data_ptr()), b["n_chunks"], base,
+                                     int(k == len(tables) - 1), max_norm, int(self.skip_nonfinite), ws, rec, st),
+                  "dfn_grad_stats")
+            base += b["n_chunks"]
+        for group, b in tables:
+            b1, b2 = group["betas"]
+            b["t"] += 1
+            t = b["t"]
+            check(lib.dfn_adam_multi_guarded(C.c_void_p(b["items"].data_ptr()), C.c_void_p(b["chunks"].data_ptr()),
+                                             b["n_chunks"], float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                             float(1.0 - b1 ** t), float(math.sqrt(1.0 - b2 ** t)), t, rec, st),
+                  "dfn_adam_multi_guarded")
+            _bump_versions(b["ps"])
         return loss
 
     def _fallback(self, stream):

@@ -17,6 +17,7 @@ formed out of place; --render_final_video (broken upstream: .reshape on a list, 
 render-person path."""
 import argparse
 import json
+import math
 import os
 import time
 
@@ -658,12 +659,40 @@ def run_network(inputs, viewdirs, decoder, z_shape, z_app, signal, head_or_torso
 def make_adam(params, lr):
     """torch.optim.Adam(lr, betas=(0.9, 0.999)) as upstream (MAIN:522-547), as optim.HipAdam: the same optimizer (update
     rule, state_dict layout) with step() as one dfn_adam_multi launch per distinct step count - torch's fused
-    multi-tensor kernel takes 104 us for the decoder's 68 tensors, the five optimizers 250 us of a 2.9 ms step."""
+    multi-tensor kernel takes 104 us for the decoder's 68 tensors, the five optimizers 250 us of a 2.9 ms step.
+
+    The gradient guard (grad_guard_env: DFN_GRAD_GUARD / DFN_MAX_GRAD_NORM in the environment) goes to EVERY optimizer made
+    here: each of the five networks is guarded on its own stream, over its own parameters.  One norm across the five would
+    need a join of their streams in front of the first update - the join the step's schedule was built to avoid (DESIGN.md
+    section 5, LABNOTES section 7)."""
     params = list(params)
     if not params or not all(p.is_cuda for p in params):
         raise RuntimeError("make_adam: the parameters must live on the GPU (HipAdam; there is no CPU path)")
     from .optim import HipAdam
-    return HipAdam(params, lr=lr, betas=(0.9, 0.999))
+    return HipAdam(params, lr=lr, betas=(0.9, 0.999), **grad_guard_env())
+
+
+def grad_guard_env(env=None):
+    """HipAdam's guard arguments from the environment (the command-line flag tables are fixed; DFN_WIDTH is the precedent):
+    DFN_GRAD_GUARD=1 skips a step whose gradients hold a NaN or an Inf, DFN_MAX_GRAD_NORM=<float> clips the total norm.
+    Both unset (or empty): {} - the unguarded step.  A value that does not parse is an error here, at start-up."""
+    env = os.environ if env is None else env
+    out = {}
+    g = str(env.get("DFN_GRAD_GUARD", "")).strip()
+    if g not in ("", "0", "1"):
+        raise ValueError(f"DFN_GRAD_GUARD={g!r}: 1 (skip steps with non-finite gradients) or 0 / unset")
+    if g == "1":
+        out["skip_nonfinite"] = True
+    m = str(env.get("DFN_MAX_GRAD_NORM", "")).strip()
+    if m:
+        try:
+            v = float(m)
+        except ValueError:
+            raise ValueError(f"DFN_MAX_GRAD_NORM={m!r}: a finite number >= 0 (the bound on the total gradient norm)") from None
+        if not math.isfinite(v) or v < 0:
+            raise ValueError(f"DFN_MAX_GRAD_NORM={m!r}: a finite number >= 0 (the bound on the total gradient norm)")
+        out["max_grad_norm"] = v
+    return out
 
 
 def create_nerf(args, dev=None):
@@ -1168,6 +1197,7 @@ def train():
     # upstream draws from the unseeded global np.random.  Nothing extra is stored in the checkpoint.
     sampler.counter = int(global_step)
     from tqdm import trange, tqdm
+    guard_on, guard_seen = getattr(opts["decoder"], "_guarded", False), 0
     for i in trange(global_step + 1, args.N_iters + 1, disable=rank != 0):
         img_i = rng.choice(i_train)
         pix = sampler.draw(frame=img_i if args.sample_rate > 0 else None)
@@ -1187,6 +1217,14 @@ def train():
             tqdm.write(msg)
             with open(os.path.join(basedir, 'loss.txt'), 'a') as f:
                 f.write(msg + "\n")
+            if guard_on:        # (optim.HipAdam's gradient guard: a line of its own when steps were skipped since the last print)
+                n_skip = opts["decoder"].grad_stats()["skipped_total"]
+                if n_skip > guard_seen:
+                    guard_seen = n_skip
+                    msg = f"[GUARD] Iter: {i} Network: decoder Skipped steps (non-finite gradient): {n_skip}"
+                    tqdm.write(msg)
+                    with open(os.path.join(basedir, 'loss.txt'), 'a') as f:
+                        f.write(msg + "\n")
         sig_tr = getattr(train_buf, "signal_trainer", None)
         if sig_tr is not None and ((i % args.i_test_person == 0 and i > 0) or i in [100, 500, 1000, 3000] or
                                    i % args.i_weights == 0):

@@ -525,6 +525,45 @@ typedef struct DfnAdamItem {
 int dfn_adam_multi(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int n_chunks, float lr, double beta1,
                    double beta2, float eps, float bias_c1, float bias_c2_sqrt, void* stream);
 
+/* ---- gradient guard: total norm, clipping and the non-finite skip in front of the optimizer step.  Stands in for what the
+ * reference had around MAIN:916-931 (the optimizer steps): torch.autograd.set_detect_anomaly(True) (HELP:5) was the only thing in
+ * its loop that noticed a bad gradient, and it is not reproduced here (it synchronises every step).  Everything below runs on
+ * the device, on the caller's stream, with no host synchronisation. */
+typedef struct DfnGradStats {
+    double sumsq;           /* sum of squares of all gradient elements of the step */
+    float norm;             /* (float)sqrt(sumsq) */
+    int32_t nonfinite;      /* number of NaN / +Inf / -Inf elements; 1 if there is none and sumsq still overflowed */
+    float clip_coef;        /* min(1, max_norm / (norm + 1e-6f)) when max_norm > 0 (torch.nn.utils.clip_grad_norm_), else 1.0f */
+    int32_t skip;           /* skip_nonfinite && (nonfinite > 0 || !isfinite(sumsq)): this step's decision */
+    int32_t skipped_total;  /* += skip by every finishing pass; never reset by the kernels (zero it when the record is made) */
+    int32_t reserved;
+} DfnGradStats;
+/* Floats of workspace for a step whose tables hold n_chunks chunks IN ALL (2 per chunk: its sum of squares, its count). */
+long dfn_grad_stats_floats(long n_chunks);
+/* Statistics of the gradients of one dfn_adam_multi table (same items / chunks, DEVICE memory), into `stats` (DEVICE memory).
+ * FIXED ORDER, no floating-point atomics - the same gradients give the same bits whatever order the blocks run in:
+ *   chunk c (one block, 256 threads): thread t squares its elements t + 256 j (j = 0..7, 0 beyond the tensor's end) in f32 and
+ *     adds them pairwise in index order, ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)); then a butterfly over the 256
+ *     threads, s = s + s[t ^ d] for d = 1, 2, 4, ..., 128; the block writes workspace[2 (chunk_base + c)] = s and the chunk's
+ *     count of non-finite elements (an int32) behind it;
+ *   finishing pass (one block, launched when `finish` != 0): sumsq = the chunk_base + n_chunks partials added in index order in
+ *     double; then the record above from max_norm (<= 0: no clipping) and skip_nonfinite.
+ * An optimizer with several tables has ONE norm, as clip_grad_norm_ has over its parameter list: call once per table with
+ * chunk_base = the chunks of the tables before it and finish = 1 in the last call only (so skipped_total moves once per step).
+ * Two launches for one table.  The gradients are only read: a non-finite value is data, never an index or a loop bound. */
+int dfn_grad_stats(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int n_chunks, long chunk_base, int finish,
+                   float max_norm, int skip_nonfinite, float* workspace, DfnGradStats* stats_dev, void* stream);
+/* dfn_adam_multi behind dfn_grad_stats on the same stream: if stats->skip the launch writes nothing (param, exp_avg and
+ * exp_avg_sq keep their bits); otherwise the same update with g = grad[i] * stats->clip_coef.  The gradient buffer itself is NOT
+ * scaled (unlike torch's in-place clip): the training step hands out the same views every step and other streams may still read
+ * them.  Step count under skips: a skipped step does not count (GradScaler + torch's fused Adam).  The host keeps counting
+ * launches (t_host, no synchronisation); the kernel steps at t_eff = t_host - stats->skipped_total: with skipped_total == 0 it
+ * uses bias_c1 / bias_c2_sqrt as passed (bit-identical to dfn_adam_multi), otherwise 1 - beta1^t_eff and sqrt(1 - beta2^t_eff)
+ * recomputed in double, once per block. */
+int dfn_adam_multi_guarded(const DfnAdamItem* items_dev, const int32_t* chunks_dev, int n_chunks, float lr, double beta1,
+                           double beta2, float eps, float bias_c1, float bias_c2_sqrt, long t_host,
+                           const DfnGradStats* stats_dev, void* stream);
+
 /* ---- Decoder.forward on explicit points: replaces DEC:277-349 -------------------------------------------
  * points, dirs [n,3]; feat [n,3] (after sigmoid), sigma [n] (raw). */
 int dfn_decoder_fwd(int tier, int field, const void* packed, const float* bias, const float* points,
