@@ -944,6 +944,113 @@ int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, cons
                                .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
 }
 
+// ---- ray gradients of the fused step (f32 tier) ---------------------------------------------------------------------------------
+// the _rays_z forms + d_norm: the shared checks (under the entry point's own name), then the <.., RAYS, DN> kernels
+static int composite_bwd_zg_impl(const BwdReq& q, float* d_norm) {
+    const std::string who = q.who;
+    if (!d_norm) return fail(DFN_E_ARG, who + ": d_norm is NULL (" + (q.hier ? "dfn_composite_bwd_hier_rays_z" : "dfn_composite_bwd_rays_z") +
+                                        " is the form without the norm gradients)");
+    const DfnFrame* frame = q.frame;
+    if (!q.rays) return fail(DFN_E_ARG, who + ": rays is NULL");
+    if (q.zero_buf && (((unsigned long)q.zero_buf & 15) || q.zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
+    if (frame && frame->fields != 2)
+        return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
+    if (!frame || !q.samples || (q.hier && (!q.z_all || !q.ranks)) || !q.d_rgb_head || !q.dsamples || (!q.bg_f32 && !q.bg_u8))
+        return fail(DFN_E_ARG, who + ": bad argument");
+    if (q.hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
+        return fail(DFN_E_ARG, who + ": 64 coarse + 64 or 128 fine samples");
+    if (!q.hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
+        return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (dfn_composite_bwd_hier_rays_zg)");
+    if (frame->ray_count <= 0) return DFN_OK;
+    CompositeBwdRaysGArgs A{};
+    A.frame = *frame;
+    A.bg_f32 = q.bg_f32;
+    A.bg_u8 = q.bg_u8;
+    A.samples = q.samples;
+    A.d_rgb_head = q.d_rgb_head;
+    A.d_rgb_com = q.d_rgb_com;
+    A.dsamples = q.dsamples;
+    A.z_all = q.z_all;
+    A.ranks = q.ranks;
+    A.zero_buf = q.zero_buf;
+    A.zero_floats = q.zero_buf ? q.zero_floats : 0;
+    A.rays = q.rays;
+    A.bounds = q.bounds;
+    A.d_norm = d_norm;
+    return launched(launch_composite_bwd_rays_g(A, q.hier, (hipStream_t)q.stream),
+                    q.hier ? "composite_bwd_hier_kernel(rays, d_norm)" : "composite_bwd_kernel(rays, d_norm)");
+}
+int dfn_composite_bwd_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                              const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                              long zero_floats, float* d_norm, void* stream) {
+    return composite_bwd_zg_impl({.who = "dfn_composite_bwd_rays_zg", .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds, .bg_f32 = bg_f32,
+                                  .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
+                                  .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream}, d_norm);
+}
+int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                   float* d_norm, void* stream) {
+    return composite_bwd_zg_impl({.who = "dfn_composite_bwd_hier_rays_zg", .hier = true, .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds,
+                                  .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head,
+                                  .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream},
+                                 d_norm);
+}
+// the tier argument of the two ray-gradient entry points: f32 only
+static int ray_grad_tier(int tier, const char* who) {
+    if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;
+    if (tier != DFN_TIER_F32)
+        return fail(DFN_E_ARG, std::string(who) + ": ray gradients run in the f32 tier (DFN_TIER_F32: the recorded arrays of the 16-bit tier are "
+                               "MX-fp8 / MX-fp4 blocks, and pose gradients are small and precision-sensitive)");
+    return DFN_OK;
+}
+int dfn_points_grad(int tier, int field, long NP, const float* params, const void* act_T, const void* dy_T, float* g_x, float* g_dhat,
+                    void* stream) {
+    if (ray_grad_tier(tier, "dfn_points_grad") != DFN_OK) return DFN_E_ARG;
+    if (!train_field_ok(field)) return fail(DFN_E_ARG, "dfn_points_grad: bad field");
+    if (!params || !act_T || !dy_T || !g_x || !g_dhat) return fail(DFN_E_ARG, "dfn_points_grad: NULL pointer (params, act_T, dy_T, g_x, g_dhat)");
+    if (NP <= 0 || NP % 32) return fail(DFN_E_ARG, "dfn_points_grad: bad argument (NP must be a positive multiple of 32)");
+    PointsGradArgs A{};
+    A.params = params;
+    A.act_T = (const float*)act_T;
+    A.dy_T = (const float*)dy_T;
+    A.g_x = g_x;
+    A.g_dhat = g_dhat;
+    A.n_tiles = NP / 32;
+    const bool lis = field == DFN_FIELD_LISTENER;
+    A.w_in = param_offset(lis ? P_FCINL_W : P_FCIN_W);
+    A.ld_in = param_shape(lis ? P_FCINL_W : P_FCIN_W).cols;
+    A.w_skip = param_offset(lis ? P_FCPSKL_W : P_FCPSK_W);
+    A.ld_skip = param_shape(lis ? P_FCPSKL_W : P_FCPSK_W).cols;
+    return launched(launch_points_grad(bwd_field(field), A, (hipStream_t)stream), "points_grad_kernel");
+}
+int dfn_rays_grad(int tier, const DfnFrame* frame, const float* rays, const float* bounds, const float* z_all, const uint8_t* ranks,
+                  const float* g_x_head, const float* g_dhat_head, const float* g_x_torso, const float* g_dhat_torso, const float* d_norm,
+                  float* d_rays, void* stream) {
+    if (ray_grad_tier(tier, "dfn_rays_grad") != DFN_OK) return DFN_E_ARG;
+    if (!frame || !rays || !g_x_head || !g_dhat_head || !g_x_torso || !g_dhat_torso || !d_norm || !d_rays)
+        return fail(DFN_E_ARG, "dfn_rays_grad: NULL pointer (frame, rays, g_x_*, g_dhat_*, d_norm, d_rays)");
+    const bool hier = frame->n_fine != 0;
+    if (hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
+        return fail(DFN_E_ARG, "dfn_rays_grad: 64 coarse + 64 or 128 fine samples");
+    if (!hier && !coarse_ok(frame->n_coarse)) return fail(DFN_E_ARG, "dfn_rays_grad: 32, 64 or 128 coarse samples");
+    if (hier && (!z_all || !ranks)) return fail(DFN_E_ARG, "dfn_rays_grad: the hierarchical step needs z_all and ranks");
+    if (frame->ray_count <= 0) return DFN_OK;
+    RaysGradArgs A{};
+    A.frame = *frame;
+    A.rays = rays;
+    A.bounds = bounds;
+    A.z_all = z_all;
+    A.ranks = ranks;
+    A.g_x[0] = g_x_head;
+    A.g_dhat[0] = g_dhat_head;
+    A.g_x[1] = g_x_torso;
+    A.g_dhat[1] = g_dhat_torso;
+    A.d_norm = d_norm;
+    A.d_rays = d_rays;
+    return launched(launch_rays_grad(A, (hipStream_t)stream), "rays_grad_kernel");
+}
+
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,
                 const uint32_t* masks, long NP, void* dy_T, void* stream) {
     if (no_width(tier, "dfn_mlp_bwd") != DFN_OK) return DFN_E_ARG;

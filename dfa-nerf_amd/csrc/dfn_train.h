@@ -43,12 +43,47 @@ struct CompositeBwdRaysArgs : CompositeBwdArgs {
     const float* bounds;
 };
 
+// ... and the ray-gradient forms of those two (dfn_composite_bwd_rays_zg / _hier_rays_zg: the <.., RAYS, DN> kernels) also leave the
+// gradient of the two ray norms: d_norm f32 [rays][2] = dL/d|d_head| (through the head image's dist = dz |d_head|) and dL/d|d_torso|
+// (through the composite's).  Again a block of its own behind the rays block: the kernels without it keep their argument segment
+struct CompositeBwdRaysGArgs : CompositeBwdRaysArgs {
+    float* d_norm;
+};
+
+// points_grad_kernel (f32 tier): dL/d(point) and dL/d(unit view direction) of every evaluated point of one field, from the arrays a
+// backward leaves behind (dy_T: the pre-activation gradients, act_T: the recorded positional encodings) and the flat parameters
+struct PointsGradArgs {
+    const float* params;        // flat decoder parameters (f32, state_dict order)
+    const float* act_T;         // [NP/32][RecMap rows][32]
+    const float* dy_T;          // [NP/32][GradMap rows][32]
+    float* g_x;                 // out [NP][3]
+    float* g_dhat;              // out [NP][3]
+    long n_tiles;               // NP / 32
+    int w_in, ld_in;            // head / listener: offset and row length of the input layer's weight in `params` (the first 60 columns are used)
+    int w_skip, ld_skip;        // ... and of the skip layer's
+};
+// rays_grad_kernel: the per-ray sums of those (one wave per ray) -> d_rays [rays][12] in the layout of `rays`
+struct RaysGradArgs {
+    DfnFrame frame;             // ray_count, n_coarse, n_fine, z_near / z_far (bounds == null)
+    const float* rays;          // [rays][12]
+    const float* bounds;        // [rays][2] or null
+    const float* z_all;         // hierarchical step: [rays][S] merged depths ...
+    const unsigned char* ranks; // ... and the merged rank of evaluated point j
+    const float* g_x[2];        // per field [NP][3], evaluation order
+    const float* g_dhat[2];
+    const float* d_norm;        // [rays][2]
+    float* d_rays;              // out [rays][12]
+};
+
 hipError_t launch_mlp_bwd(int tier, int field, const MlpBwdArgs& A, hipStream_t st);
 hipError_t launch_mlp_bwd_bf16(bool torso, const MlpBwdArgs& A, hipStream_t st);     // dfn_bwd_bf16.hip
 void bwd_program_info(int tier, int field, ProgramInfo* out);
 hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st);
 hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st);      // n_fine in {64, 128}
 hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st);      // fields == 2; counts as the two above
+hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier, hipStream_t st);  // ... + d_norm
+hipError_t launch_points_grad(int field, const PointsGradArgs& A, hipStream_t st);                 // f32 tier; field 0 head, 1 torso, 2 listener
+hipError_t launch_rays_grad(const RaysGradArgs& A, hipStream_t st);
 // Split-K partials: C [ksplit][c_stride] and dbias [ksplit][n_bias], one writer per element and slice (no atomics);
 // launch_reduce_scatter / launch_reduce_bias add the slices in index order (bit-reproducible gradients).
 // f32 tier: wgrad_full_kernel + wgrad_narrow_kernel (dfn_plan.h: WNItem)

@@ -61,8 +61,27 @@ __device__ __forceinline__ void composite_zero_fill(const CompositeBwdArgs& A) {
     if (blockIdx.x == 0 && threadIdx.x < (A.zero_floats & 3)) A.zero_buf[(n4 << 2) + threadIdx.x] = 0.f;
 }
 // the argument block of the compositing backward kernels: the plain block, or the rays form's longer one (dfn_train.h)
-template <bool RAYS> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
-template <> struct CompositeArgsOf<true> { typedef CompositeBwdRaysArgs type; };
+// (DN: the ray-gradient forms, which also write d_norm - always with RAYS)
+template <bool RAYS, bool DN = false> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
+template <> struct CompositeArgsOf<true, false> { typedef CompositeBwdRaysArgs type; };
+template <> struct CompositeArgsOf<true, true> { typedef CompositeBwdRaysGArgs type; };
+// sum over the wave in a fixed order: partners at XOR distance 32, 16, 8, 4, 2, 1 (oracle: wave_sum64); every lane ends with the sum
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// DN kernels: dL/d|d| of one image = (1 / |d|) sum_s dL/d(s_s) (s_s + 1e-6), s = the effective density weights_bwd_n / image_bwd
+// differentiated (alpha_s = 1 - exp(-(s_s + 1e-6) dz_s |d|): the norm reaches the image through dist only).  A lane adds its own
+// positions in index order, wave_sum_xor adds the lanes; lane 0 writes
+template <int N>
+__device__ __forceinline__ float norm_grad(const float (&ds)[N], const float (&s)[N], const bool (&live)[N], float nrm) {
+    float p = 0.f;
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        if (live[k]) p += ds[k] * (fmaxf(s[k], 0.f) + 1e-6f);
+    return wave_sum_xor(p) / nrm;
+}
 // RAYS kernels (dfn_composite_bwd_rays_z / _hier_rays_z): the norms of the two directions of row `ray` of A.rays (o_head, d_head,
 // o_torso, d_torso), in the arithmetic of the forward's norm3 (dfn_render_kernels.h)
 __device__ __forceinline__ void ray_row_norms(const float* rays, long ray, float (&nrm)[2]) {
@@ -72,6 +91,18 @@ __device__ __forceinline__ void ray_row_norms(const float* rays, long ray, float
         const float d0 = d[0], d1 = d[1], d2 = d[2];
         nrm[b] = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
     }
+}
+// the coarse depths in the forward's arithmetic (MAIN:617-618; torch.linspace(0, 1, NC): lower half step * i, upper half 1 - step *
+// (NC - 1 - i) as one fma), for rays_grad_kernel.  composite_bwd_kernel keeps the lambdas it has always had (tval / zval, the same
+// operations): written through these helpers the plain <1, false> instantiation came out with a different instruction stream, and
+// the existing kernels' ISA is held fixed.  tests/test_gpu_ray_grad.py holds the two statements together bit for bit
+// (test_rays_grad_depths_are_the_forwards).
+__device__ __forceinline__ float coarse_step(int NC) { return __fdiv_rn(1.0f, (float)(NC - 1)); }
+__device__ __forceinline__ float coarse_t(float step, int NC, int i) {
+    return (i < NC / 2) ? __fmul_rn(step, (float)i) : fmaf(-step, (float)(NC - 1 - i), 1.0f);
+}
+__device__ __forceinline__ float coarse_depth(float z_near, float z_far, float t) {
+    return __fadd_rn(__fmul_rn(z_near, __fsub_rn(1.0f, t)), __fmul_rn(z_far, t));
 }
 // KL consecutive samples per lane (KL = 1: --N_samples 32 / 64, lanes beyond the ray's samples idle; KL = 2: 128), round 6.
 // Sample i = lane KL + k.  The scans run over the lanes' local products / sums and are carried across a lane's KL positions;
@@ -108,8 +139,10 @@ __device__ __forceinline__ void weights_bwd_n(const float (&sigma)[KL], const fl
 }
 // RAYS: the step on caller-supplied rays - the norms from the directions of row `ray`, the depths between that ray's (near, far) when
 // bounds are given, the background of the last sample from row `ray`; everything behind the geometry is the same code
-template <int KL, bool RAYS = false>
-__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS>::type A) {
+// DN (with RAYS): also d_norm[ray] = (dL/d|d_head|, dL/d|d_torso|), the ray-gradient step's input (dfn_composite_bwd_rays_zg)
+template <int KL, bool RAYS = false, bool DN = false>
+__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN>::type A) {
+    static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
     composite_zero_fill(A);
     const int lane = threadIdx.x & 63;
     const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -192,6 +225,13 @@ __global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS>::type 
             q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
         }
         weights_bwd_n<KL>(s1, dist, q, live, lane, r);
+        if constexpr (DN) {
+            float dsv[KL];
+#pragma unroll
+            for (int k = 0; k < KL; ++k) dsv[k] = r[k].ds;
+            const float g = norm_grad<KL>(dsv, s1, live, nrm[0]);
+            if (lane == 0) A.d_norm[ray * 2] = g;
+        }
 #pragma unroll
         for (int k = 0; k < KL; ++k) {
             d_sg_h[k] = (sg_h[k] > 0.f) ? r[k].ds : 0.f;
@@ -225,6 +265,13 @@ __global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS>::type 
             dist[k] = dz[k] * nrm[1];
         }
         weights_bwd_n<KL>(ssum, dist, q, live, lane, r);
+        if constexpr (DN) {
+            float dsv[KL];
+#pragma unroll
+            for (int k = 0; k < KL; ++k) dsv[k] = r[k].ds;
+            const float g = norm_grad<KL>(dsv, ssum, live, nrm[1]);
+            if (lane == 0) A.d_norm[ray * 2 + 1] = g;
+        }
 #pragma unroll
         for (int k = 0; k < KL; ++k) {
             const float gch = ch[k][0] * Gc[0] + ch[k][1] * Gc[1] + ch[k][2] * Gc[2];
@@ -276,8 +323,9 @@ hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st) {
 // merged depths; the fine depths are constants (no gradient through sample_pdf), so this is the same differentiation as
 // composite_bwd_kernel with run-time depths and the scans carried across a lane's K positions.
 // RAYS: as in composite_bwd_kernel - the norms and the background row only (the depths are z_all's)
-template <int K, bool RAYS = false>
-__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS>::type A) {
+template <int K, bool RAYS = false, bool DN = false>
+__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS, DN>::type A) {
+    static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
     constexpr int S = 64 * K;
     __shared__ unsigned char inv_s[4][S];
     composite_zero_fill(A);
@@ -365,6 +413,9 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
             later += w[k] * q[k];
         }
     };
+    bool all_live[K];              // (DN: every merged position holds a sample)
+#pragma unroll
+    for (int k = 0; k < K; ++k) all_live[k] = true;
     float d_sg_h[K], d_sg_t[K], d_ch[K][3], d_ct[K][3];
     {   // head-only image
         float s1[K], dist[K], q[K], w[K], ds[K];
@@ -376,6 +427,10 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
             q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
         }
         image_bwd(s1, dist, q, w, ds);
+        if constexpr (DN) {
+            const float g = norm_grad<K>(ds, s1, all_live, nrm[0]);
+            if (lane == 0) A.d_norm[ray * 2] = g;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const bool h_is_bg = cbg && lastp[k];
@@ -409,6 +464,10 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
             q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
         }
         image_bwd(ss, dist, q, w, ds);
+        if constexpr (DN) {
+            const float g = norm_grad<K>(ds, ss, all_live, nrm[1]);
+            if (lane == 0) A.d_norm[ray * 2 + 1] = g;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const bool h_is_bg = cbg && lastp[k];
@@ -459,6 +518,230 @@ hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, h
         if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, true>), dim3(blocks), dim3(256), 0, st, A);
         else hipLaunchKernelGGL((composite_bwd_kernel<1, true>), dim3(blocks), dim3(256), 0, st, A);
     }
+    return hipGetLastError();
+}
+// ... and with the norm gradients (dfn_composite_bwd_rays_zg / _hier_rays_zg): instantiations of their own next to the ones above
+hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier, hipStream_t st) {
+    const int blocks = (A.frame.ray_count + 3) / 4;
+    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
+    if (!A.rays || !A.d_norm || A.frame.fields != 2) return hipErrorInvalidValue;
+    if (hier) {
+        if (nc != 64 || (A.frame.n_fine != 64 && A.frame.n_fine != 128)) return hipErrorInvalidValue;
+        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, true, true>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, true, true>), dim3(blocks), dim3(256), 0, st, A);
+    } else {
+        if ((nc != 128 && nc != 64 && nc != 32) || A.frame.n_fine != 0) return hipErrorInvalidValue;
+        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, true, true>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_bwd_kernel<1, true, true>), dim3(blocks), dim3(256), 0, st, A);
+    }
+    return hipGetLastError();
+}
+
+// ================================================================================================
+// ray gradients (f32 tier): the backward chains stop at the first layer's pre-activation gradient (bwd_head: dy0; bwd_torso: DE0 / DS0);
+// these two kernels carry it one GEMM further, through the positional encoding, to the points and on to the rays.
+// Differentiates decoder.py:257-275 (positional encoding), :291-311, :321-325 (the layers that read it), :109-134 (deformation field),
+// :337-340 (view direction) and run_nerf_com_trainExpLater.py:638-641 (p = o + d z).
+// ================================================================================================
+// points_grad_kernel: one wave = one 32-point tile.  Gradient on the positional encoding G_pe[60][32] = sum over the layers that
+// read the encoding of W[:, :60]^T x dy (head: fc_in x dy0 + fc_p_skips x g4; torso: the residual's rows S_DEO + blocks_embed.0 x DE0 +
+// blocks_signal.0 x DS0 + fc_embed_skips.0 x GE3) and on the view encoding G_v[24][32] = fc_view^T x dyv, as 32x32x2 f32 MFMAs: A = the
+// weight slice (staged once per workgroup in LDS, [k][60] / [k][24]; MFMA row i = encoding column i, rows beyond the slice read its
+// last column and are never used), B = the tile's dy_T rows straight from memory (rows 2 kk, 2 kk + 1 = one 256-byte line per MFMA).
+// Then the encoding's backward in registers, with the sin / cos values the forward recorded: column j = 6 o + 3 c + a holds
+// sin (c = 0) / cos (c = 1) of c_o x_a / 2, so g_x[a] = sum_o (c_o / 2) (G_sin cos - G_cos sin).
+// Order of every sum: the MFMA chain runs over k ascending, term after term as listed; a lane adds its 16 accumulator rows per tile in
+// register order (tile 0, then 1), then lane n + 32 is added to lane n.  No atomics: one writer per output.
+template <typename K> static hipError_t lds_attr_once(K kernel, int bytes, bool (&done)[64]);     // (below, with the weight gradients)
+constexpr int PG_THREADS = 512, PG_WAVES = PG_THREADS / 64;
+template <bool TORSO> struct PGShape {
+    static constexpr int K = TORSO ? DH : HID;                  // rows of every weight slice that meets the encoding
+    static constexpr int TERMS = TORSO ? 3 : 2;
+    static constexpr int LDS_FLOATS = TERMS * K * NPE + HID * NPEV;
+};
+// acc[NT] += W^T x dy over K rows: w = the LDS slice [K][NC], dy = the tile's rows [K][32]
+template <int NT, int K, int NC>
+__device__ __forceinline__ void pg_gemm(f32x16 (&acc)[NT], const lds_f32* w, const float* dy, int n, int h) {
+    int col[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) col[t] = (32 * t + n < NC) ? 32 * t + n : NC - 1;
+#pragma unroll 8
+    for (int kk = 0; kk < K / 2; ++kk) {
+        const int k = 2 * kk + h;
+        const float b = dy[k * 32 + n];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[k * NC + col[t]], b, acc[t], 0, 0, 0);
+    }
+}
+// g[a] += the encoding's backward over the rows this lane holds of `acc` (NT tiles, NCOL valid columns); enc = the tile's recorded rows
+template <int NT, int NCOL>
+__device__ __forceinline__ void pg_posenc_bwd(const f32x16 (&acc)[NT], const float* enc, const float* extra, int n, int h, float (&g)[3]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = 32 * t + tile_feat(h, r);
+            if (j >= NCOL) continue;
+            const int o = j / 6, m = j - 6 * o, a = m >= 3 ? m - 3 : m;
+            const bool is_cos = m >= 3;
+            float G = acc[t][r];
+            if (extra) G += extra[j * 32 + n];                          // (torso: the residual deform(p) + p)
+            const float other = enc[(is_cos ? j - 3 : j + 3) * 32 + n];   // the cos of a sin column, the sin of a cos column
+            const float half_c = ldexpf(3.14159265358979323846f, o - 1);  // fl32(2^o pi) / 2, exact
+            const float term = (is_cos ? -half_c : half_c) * G * other;
+            g[0] += a == 0 ? term : 0.f;
+            g[1] += a == 1 ? term : 0.f;
+            g[2] += a == 2 ? term : 0.f;
+        }
+}
+template <bool TORSO>
+__global__ __launch_bounds__(PG_THREADS) void points_grad_kernel(const PointsGradArgs A) {
+    using S = PGShape<TORSO>;
+    constexpr int K = S::K;
+    extern __shared__ __attribute__((aligned(16))) char pg_smem[];
+    lds_f32* lds = (lds_f32*)pg_smem;
+    // the weight slices: [term][K][60], then fc_view [256][24]
+    {
+        int off[3], ld[3];
+        if constexpr (TORSO) {
+            off[0] = param_offset(P_DE0_W); ld[0] = NPE + NET;
+            off[1] = param_offset(P_DS0_W); ld[1] = NPE + NET;
+            off[2] = param_offset(P_DESK_W); ld[2] = NPE;
+        } else {
+            off[0] = A.w_in; ld[0] = A.ld_in;
+            off[1] = A.w_skip; ld[1] = A.ld_skip;
+            off[2] = 0; ld[2] = 0;
+        }
+#pragma unroll
+        for (int q = 0; q < S::TERMS; ++q)
+            for (int i = threadIdx.x; i < K * NPE; i += PG_THREADS) {
+                const int k = i / NPE, j = i - k * NPE;
+                lds[q * K * NPE + i] = A.params[off[q] + k * ld[q] + j];
+            }
+        for (int i = threadIdx.x; i < HID * NPEV; i += PG_THREADS) lds[S::TERMS * K * NPE + i] = A.params[param_offset(P_FCV_W) + i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, h = lane >> 5;
+    constexpr int g_rows = TORSO ? GradMap::S_ROWS : GradMap::H_ROWS, a_rows = TORSO ? RecMap::S_ROWS : RecMap::H_ROWS;
+    constexpr int gt = TORSO ? GradMap::S_TRUNK : GradMap::H_TRUNK, rt = TORSO ? RecMap::S_TRUNK : RecMap::H_TRUNK;
+    for (long tile = (long)blockIdx.x * PG_WAVES + wave; tile < A.n_tiles; tile += (long)gridDim.x * PG_WAVES) {
+        const float* dy = A.dy_T + tile * (long)g_rows * 32;
+        const float* act = A.act_T + tile * (long)a_rows * 32;
+        f32x16 acc[2], accv[1];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = accv[0][r] = 0.f;
+        if constexpr (TORSO) {
+            pg_gemm<2, K, NPE>(acc, lds, dy + GradMap::S_DE0 * 32, n, h);
+            pg_gemm<2, K, NPE>(acc, lds + K * NPE, dy + GradMap::S_DS0 * 32, n, h);
+            pg_gemm<2, K, NPE>(acc, lds + 2 * K * NPE, dy + GradMap::S_GE3 * 32, n, h);
+        } else {
+            pg_gemm<2, K, NPE>(acc, lds, dy + (gt + GradMap::T_DY0) * 32, n, h);
+            pg_gemm<2, K, NPE>(acc, lds + K * NPE, dy + (gt + GradMap::T_G4) * 32, n, h);
+        }
+        pg_gemm<1, HID, NPEV>(accv, lds + S::TERMS * K * NPE, dy + (gt + GradMap::T_DYV) * 32, n, h);
+        float gx[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
+        pg_posenc_bwd<2, NPE>(acc, act + (TORSO ? RecMap::S_PE : RecMap::H_PE) * 32, TORSO ? dy + GradMap::S_DEO * 32 : nullptr, n, h, gx);
+        pg_posenc_bwd<1, NPEV>(accv, act + (rt + RecMap::T_VIEW) * 32, nullptr, n, h, gd);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            gx[a] += __shfl_xor(gx[a], 32);
+            gd[a] += __shfl_xor(gd[a], 32);
+        }
+        if (h == 0) {
+            const long p = tile * 32 + n;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                A.g_x[p * 3 + a] = gx[a];
+                A.g_dhat[p * 3 + a] = gd[a];
+            }
+        }
+    }
+}
+hipError_t launch_points_grad(int field, const PointsGradArgs& A, hipStream_t st) {
+    if (!A.params || !A.act_T || !A.dy_T || !A.g_x || !A.g_dhat || A.n_tiles <= 0) return hipErrorInvalidValue;
+    const bool torso = field == FIELD_TORSO;
+    const int lds = (torso ? PGShape<true>::LDS_FLOATS : PGShape<false>::LDS_FLOATS) * 4;
+    static_assert(PGShape<false>::LDS_FLOATS * 4 <= 160 * 1024, "LDS budget of points_grad_kernel");
+    // the head's slices fill a compute unit's LDS (144 KiB): one workgroup per unit; the torso's (69 KiB) leave room for two
+    const long want = (A.n_tiles + PG_WAVES - 1) / PG_WAVES, cap = torso ? 512 : 256;
+    const int blocks = (int)(want < cap ? want : cap);
+    hipError_t e;
+    if (torso) {
+        static bool done[64] = {};
+        if ((e = lds_attr_once(points_grad_kernel<true>, lds, done)) != hipSuccess) return e;
+        hipLaunchKernelGGL(points_grad_kernel<true>, dim3(blocks), dim3(PG_THREADS), lds, st, A);
+    } else {
+        static bool done[64] = {};
+        if ((e = lds_attr_once(points_grad_kernel<false>, lds, done)) != hipSuccess) return e;
+        hipLaunchKernelGGL(points_grad_kernel<false>, dim3(blocks), dim3(PG_THREADS), lds, st, A);
+    }
+    return hipGetLastError();
+}
+
+// rays_grad_kernel: one wave per ray.  Evaluated point j of ray r (j = lane, lane + 64, ...: the order of samples / act_T / g_x) sits at
+// depth z_j - coarse step: near (1 - t_j) + far t_j with that ray's bounds or the frame's pair, in the forward's arithmetic;
+// hierarchical step: z_all[r][ranks[r][j]] - and x_j = o + z_j d, dhat = d / |d|, so
+//   g_o = sum_j g_x_j,   g_d = sum_j z_j g_x_j + (I - dhat dhat^T) / |d| sum_j g_dhat_j + g_|d| dhat      per field,
+// with g_|d| from the compositing backward (d_norm: the head image measures its distances with |d_head|, the composite with |d_torso|).
+// Order: a lane adds its points j = lane, lane + 64, ... in that order, then the butterfly of wave_sum_xor (XOR 32, 16, ..., 1).
+__global__ __launch_bounds__(256) void rays_grad_kernel(const RaysGradArgs A) {
+    const int lane = threadIdx.x & 63;
+    const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ray >= A.frame.ray_count) return;
+    const int NC = A.frame.n_coarse, S = NC + A.frame.n_fine;
+    const bool hier = A.frame.n_fine > 0;
+    const float near = A.bounds ? A.bounds[ray * 2] : A.frame.z_near, far = A.bounds ? A.bounds[ray * 2 + 1] : A.frame.z_far;
+    const float step = coarse_step(NC);
+    float sx[2][3] = {}, szx[2][3] = {}, sd[2][3] = {};
+    for (int j = lane; j < S; j += 64) {
+        float z;
+        if (hier) {
+            z = A.z_all[ray * S + A.ranks[ray * S + j]];
+        } else {
+            z = coarse_depth(near, far, coarse_t(step, NC, j));
+        }
+        const long p = ray * S + j;
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float gx = A.g_x[f][p * 3 + a];
+                sx[f][a] += gx;
+                szx[f][a] += z * gx;
+                sd[f][a] += A.g_dhat[f][p * 3 + a];
+            }
+    }
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            sx[f][a] = wave_sum_xor(sx[f][a]);
+            szx[f][a] = wave_sum_xor(szx[f][a]);
+            sd[f][a] = wave_sum_xor(sd[f][a]);
+        }
+    if (lane != 0) return;
+    float nrms[2];
+    ray_row_norms(A.rays, ray, nrms);                  // (the forward's norm3 arithmetic)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+        const float* d = A.rays + ray * 12 + 6 * f + 3;
+        const float nrm = nrms[f];
+        const float dh[3] = {d[0] / nrm, d[1] / nrm, d[2] / nrm};
+        const float dot = (dh[0] * sd[f][0] + dh[1] * sd[f][1]) + dh[2] * sd[f][2];
+        const float gn = A.d_norm[ray * 2 + f];
+        float* out = A.d_rays + ray * 12 + 6 * f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            out[a] = sx[f][a];
+            out[3 + a] = (szx[f][a] + (sd[f][a] - dh[a] * dot) / nrm) + gn * dh[a];
+        }
+    }
+}
+hipError_t launch_rays_grad(const RaysGradArgs& A, hipStream_t st) {
+    const int nc = A.frame.n_coarse, nf = A.frame.n_fine;
+    if (!A.rays || !A.g_x[0] || !A.g_x[1] || !A.g_dhat[0] || !A.g_dhat[1] || !A.d_norm || !A.d_rays) return hipErrorInvalidValue;
+    if (nf ? (nc != 64 || (nf != 64 && nf != 128) || !A.z_all || !A.ranks) : (nc != 32 && nc != 64 && nc != 128)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rays_grad_kernel, dim3((A.frame.ray_count + 3) / 4), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 

@@ -114,6 +114,11 @@ def _load():
                                           vp]),
         "dfn_composite_bwd_rays_z": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, lg, vp]),
         "dfn_composite_bwd_hier_rays_z": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, vp, fp, fp, fp, fp, lg, vp]),
+        # ray gradients of that step (f32): the _rays_z forms + d_norm, the per-point and the per-ray kernel
+        "dfn_composite_bwd_rays_zg": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, lg, fp, vp]),
+        "dfn_composite_bwd_hier_rays_zg": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, vp, fp, fp, fp, fp, lg, fp, vp]),
+        "dfn_points_grad": (i32, [i32, i32, lg, fp, vp, vp, fp, fp, vp]),
+        "dfn_rays_grad": (i32, [i32, C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, fp, vp]),
         "dfn_train_loss_floats": (lg, [i32]),
         "dfn_train_fwd_loss": (i32, [i32, C.POINTER(DfnFrame), vp, vp, fp, fp, fp, vp, ip, fp, fp, fp, vp, vp, vp, vp,
                                      C.POINTER(DfnTrainLoss), vp]),

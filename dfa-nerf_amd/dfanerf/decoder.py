@@ -161,7 +161,10 @@ class Decoder(nn.Module):
         from . import engine
         field = 1 if head_or_torso == 'torso' else (0 if signal is not None else 2)
         needs_grad = torch.is_grad_enabled() and (
-            any(p.requires_grad for p in self.parameters()) or (signal is not None and signal.requires_grad))
+            any(p.requires_grad for p in self.parameters()) or (signal is not None and signal.requires_grad) or
+            (tier in ("f32", 0) and (p_in.requires_grad or ray_d.requires_grad)))
+        # (points / directions that require grad: the f32 tier differentiates them - DecoderTrainFn -; in every other tier, and with
+        #  nothing else to train there, they are constants as they always were)
         if needs_grad:
             from . import training
             return training.decoder_train(self, field, p_in, ray_d, z_shape, z_app, signal, tier)

@@ -173,6 +173,10 @@ class TrainBuffers:
                                      device=device) for f in (0, 1)]
         self.nb = [check(lib.dfn_bias_floats(self.tier, f), "bias") for f in (0, 1)]
         self.bias = torch.empty(self.nb[0] + self.nb[1], dtype=torch.float32, device=device)
+        # ray gradients (f32 tier, rays that require grad; allocated by the first backward that needs them): per field [2, NP, 3] =
+        # (dL/d point, dL/d unit view direction) of every evaluated point, and the gradient of the two ray norms [n_rays, 2]
+        self.g_pts = None
+        self.d_norm = None
 
     def bind(self, dec):
         """Parameter list of `dec` in state_dict order and the matching views of one flat buffer (_FlatNet.of: one per
@@ -203,15 +207,20 @@ class FusedTrainFn(torch.autograd.Function):
 
 class FusedTrainRaysFn(torch.autograd.Function):
     """FusedTrainFn on caller-supplied rays [n,12] (o_head, d_head, o_torso, d_torso) with optional per-ray bounds [n,2]:
-    dfn_train_rays_fwd[_hier] and dfn_composite_bwd[_hier]_rays_z in place of the pixel-id calls; everything else is the same step."""
+    dfn_train_rays_fwd[_hier] and dfn_composite_bwd[_hier]_rays_z in place of the pixel-id calls; everything else is the same step.
+    When `rays` requires grad (f32 tier) the backward also returns dL/d rays [n,12]: the compositing backward in its _zg form (+ the
+    gradient of the ray norms), then dfn_points_grad per field and dfn_rays_grad behind the two dX chains (_ray_gradient); bounds and
+    the fine depths stay constants.  Without it the step issues exactly the launches it always did."""
 
     @staticmethod
     def forward(ctx, sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, defer=None):
+        ctx.ray_grad = bool(ctx.needs_input_grad[5])
         return _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, None, z_shape, z_app, defer, rays=rays, bounds=bounds)
 
     @staticmethod
     def backward(ctx, d_h, d_c):
-        return _fused_backward(ctx, d_h, d_c) + (None,)       # (one input more than FusedTrainFn: rays, bounds for pix_index)
+        g = _fused_backward(ctx, d_h, d_c)      # (one input more than FusedTrainFn: rays, bounds for pix_index)
+        return g[:5] + (ctx.d_rays, None) + g[6:]
 
 
 # the fused step's entry points: forward by (caller-supplied rays, hierarchical, loss epilogue), compositing backward by the first two
@@ -220,6 +229,26 @@ _FWD_ENTRY = {(False, False, False): "dfn_train_fwd", (False, True, False): "dfn
               (True, False, False): "dfn_train_rays_fwd", (True, True, False): "dfn_train_rays_fwd_hier"}
 _BWD_ENTRY = {(False, False): "dfn_composite_bwd_z", (False, True): "dfn_composite_bwd_hier_z",
               (True, False): "dfn_composite_bwd_rays_z", (True, True): "dfn_composite_bwd_hier_rays_z"}
+# ... of the rays step when the rays require grad: the same launch + d_norm (by hierarchical)
+_BWD_ZG_ENTRY = {False: "dfn_composite_bwd_rays_zg", True: "dfn_composite_bwd_hier_rays_zg"}
+
+
+def _ray_gradient(ctx, buf, frame, stream):
+    """dL/d rays [n,12] of the step whose two dX chains have been issued on `stream` (the stream that owns dy_T): dfn_points_grad per
+    field (dL/d point, dL/d unit view direction of every evaluated point, from dy_T, the recorded encodings in act_T and the flat
+    parameters), then dfn_rays_grad (the per-ray sums, the direction's normalisation and the norm gradients the _zg compositing
+    backward left in buf.d_norm).  Three launches, no host synchronisation."""
+    dev = buf.flat.device
+    if buf.g_pts is None:
+        buf.g_pts = [torch.empty(2, buf.NP, 3, dtype=torch.float32, device=dev) for _ in (0, 1)]      # per field: g_x, g_dhat
+    for f in (0, 1):
+        check(lib.dfn_points_grad(buf.tier, f, buf.NP, _ptr(buf.flat), _ptr(buf.act[f]), _ptr(buf.dy[f]), _ptr(buf.g_pts[f][0]),
+                                  _ptr(buf.g_pts[f][1]), stream), "dfn_points_grad")
+    d_rays = torch.empty(buf.n_rays, 12, dtype=torch.float32, device=dev)
+    check(lib.dfn_rays_grad(buf.tier, C.byref(frame), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(buf.z_all), _ptr(buf.ranks),
+                            _ptr(buf.g_pts[0][0]), _ptr(buf.g_pts[0][1]), _ptr(buf.g_pts[1][0]), _ptr(buf.g_pts[1][1]),
+                            _ptr(buf.d_norm), _ptr(d_rays), stream), "dfn_rays_grad")
+    return d_rays
 
 
 def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None, rays=None, bounds=None):
@@ -294,9 +323,17 @@ def _fused_backward(ctx, d_h, d_c):
     # one entry point per form (rays or pixel ids, hierarchical or not); what differs is the ray source and the hierarchical extras
     src = (_ptr(ctx.rays), _ptr(ctx.bounds)) if ctx.rays is not None else (_ptr(ctx.pix),)
     hier = (_ptr(buf.z_all), _ptr(buf.ranks)) if buf.n_fine else ()
-    name = _BWD_ENTRY[ctx.rays is not None, bool(buf.n_fine)]
+    ray_grad = getattr(ctx, "ray_grad", False)
+    if ray_grad:
+        # the rays require grad: the same compositing backward (bit for bit) that also leaves the gradient of the two ray norms
+        name = _BWD_ZG_ENTRY[bool(buf.n_fine)]
+        if buf.d_norm is None:
+            buf.d_norm = torch.empty(buf.n_rays, 2, dtype=torch.float32, device=dev)
+        extra = (_ptr(buf.d_norm),)
+    else:
+        name, extra = _BWD_ENTRY[ctx.rays is not None, bool(buf.n_fine)], ()
     check(getattr(lib, name)(C.byref(frame), *src, _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples), *hier, _ptr(d_h), _ptr(d_c),
-                             _ptr(buf.dsamples), zb, zn, st), name)
+                             _ptr(buf.dsamples), zb, zn, *extra, st), name)
     g_bias = torch.empty(buf.nb[0] + buf.nb[1], dtype=torch.float32, device=dev)
     main = torch.cuda.current_stream(dev)
     # (with more than one rank RCCL brings a fifth stream; the package asks the runtime for eight hardware queues then
@@ -447,6 +484,9 @@ def _fused_backward(ctx, d_h, d_c):
             dx(f, st)
             dsig(f, st)
             dw(f, st, g_flat, False)
+    # dL/d rays: behind both dX chains on the stream that owns dy_T (and behind this stream's share of the weight gradients: the
+    # parameter gradients' schedule is the step's without ray gradients, launch for launch)
+    ctx.d_rays = _ray_gradient(ctx, buf, frame, st) if ray_grad else None
     buf.net.deposit(g_flat, touched=_decoder_touched(buf.net, (0, 1)))
     return (d_sig[:96].reshape(ctx.sig_shapes[0]), d_sig[96:].reshape(ctx.sig_shapes[1]), None, None, None, None,
             None, None, None)
@@ -806,6 +846,27 @@ def _check_rays(buf, bg, pix_index, rays, bounds):
                          f"{tuple(bounds.shape) if torch.is_tensor(bounds) else type(bounds).__name__}")
 
 
+def pinhole_rays(pose, pose_body, pix, H, W, focal, cx, cy):
+    """The rays [n,12] = (o_head, d_head, o_torso, d_torso) of the pixels `pix` [n] (integer, y * W + x) for a head pose and a body
+    pose ([3,4] or [4,4] camera-to-world), in plain torch ops and differentiable: what render_train(rays=...) takes when a pose, an
+    offset or an intrinsic is to be learned.  The arithmetic is get_rays' (run_nerf_helpers.py:449-465; dfn_get_rays): dx = (x - cx) /
+    focal, dy = -(y - cy) / focal, d[k] = (dx R[k,0] + dy R[k,1]) - R[k,2], o = the pose's translation."""
+    pix = torch.as_tensor(pix)
+    dev = pix.device
+    if pix.dim() != 1 or pix.dtype.is_floating_point or int(H) <= 0 or int(W) <= 0:
+        raise ValueError("pinhole_rays: pix is a 1-d integer tensor of pixel ids y * W + x")
+    y = torch.div(pix.long(), int(W), rounding_mode="floor")
+    x = (pix.long() - y * int(W)).to(torch.float32)
+    dx = (x - cx) / focal
+    dy = -(y.to(torch.float32) - cy) / focal
+    parts = []
+    for P in (pose, pose_body):
+        P = torch.as_tensor(P, dtype=torch.float32).to(dev)[:3, :4]
+        parts.append(P[:, 3].expand(pix.numel(), 3))
+        parts.append(torch.stack([(dx * P[k, 0] + dy * P[k, 1]) - P[k, 2] for k in range(3)], -1))
+    return torch.cat(parts, 1).contiguous()
+
+
 def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, signal_trainer=None, rays=None, bounds=None):
     """Differentiable (w.r.t. the decoder parameters and the two signals) two-field render of the
     pixels `pix_index` [n] (int32, y*W+x): coarse (frame.n_fine == 0, the reference's step) or hierarchical (64 / 128
@@ -816,13 +877,17 @@ def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z
     rays (with pix_index None): train on caller-supplied rays instead of the frame's pinhole rays - float32 [n,12] on the device,
     contiguous (o_head, d_head, o_torso, d_torso: engine.pack_rays; directions of any length), bg [n,3] = the background of ray r,
     bounds None or float32 [n,2] = (near, far) per ray; the frame's poses, intrinsics, H, W are ignored (FusedTrainRaysFn).  Anything
-    else is a ValueError naming the argument, before any launch."""
+    else is a ValueError naming the argument, before any launch.  Rays that require grad (f32 tier; e.g. pinhole_rays of a learnable
+    pose) get their gradient from the backward; bounds and the fine depths stay constants."""
     if rays is not None or bounds is not None:
         if rays is None:
             raise ValueError("render_train: bounds are the per-ray (near, far) of caller-supplied rays: rays is None")
         if frame.ray_count != buf.n_rays:
             raise ValueError(f"render_train: the buffers were sized for {buf.n_rays} rays, the frame has {frame.ray_count}")
         _check_rays(buf, bg, pix_index, rays, bounds)
+        if rays.requires_grad and buf.tier != 0:
+            raise ValueError("render_train: rays require grad, but the buffers are the bf16 tier's: ray gradients run in the f32 tier "
+                             "(TrainBuffers('f32', ...); detach the rays to train the 16-bit tier on them as constants)")
     if frame.ray_count != buf.n_rays or (pix_index is not None and pix_index.numel() != buf.n_rays):
         raise ValueError(f"render_train: the buffers were sized for {buf.n_rays} rays, the frame has {frame.ray_count}"
                          f" (pix_index {None if pix_index is None else pix_index.numel()})")
@@ -1041,7 +1106,9 @@ class DecoderTrainFn(torch.autograd.Function):
     """signal [96] / [42] -> feat [n,3], sigma [n] of ONE field at explicit points: dfn_fold_bias + dfn_decoder_train_fwd
     (the fused decoder with its recorder on); backward = dfn_mlp_bwd, dfn_weight_bias_grad, dfn_fold_bias_bwd: returns
     d(signal) to autograd and deposits the decoder gradients into the parameters' .grad (like FusedTrainFn).
-    The points and directions get no gradient (upstream they come from get_rays / linspace: constants)."""
+    Points and directions that require grad (f32 tier) get theirs too: dfn_points_grad behind the dX chain gives dL/d p_in and
+    dL/d(ray_d / |ray_d|), the normalisation's Jacobian (decoder.py:337) takes the latter to ray_d.  Otherwise they are constants,
+    as upstream where they come from get_rays / linspace, and the backward issues the launches it always did."""
 
     @staticmethod
     def forward(ctx, signal, net, pb, pts, dirs, zs, za):
@@ -1057,11 +1124,12 @@ class DecoderTrainFn(torch.autograd.Function):
                                         _ptr(sigma), _ptr(pb.samples), _ptr(pb.act), _ptr(pb.masks), st),
               "dfn_decoder_train_fwd")
         ctx.net, ctx.pb, ctx.keep, ctx.sig_shape = net, pb, (sg, zs, za, pts, dirs), signal.shape
+        ctx.pt_grad = (bool(ctx.needs_input_grad[3]), bool(ctx.needs_input_grad[4]))
         return feat, sigma
 
     @staticmethod
     def backward(ctx, d_feat, d_sigma):
-        net, pb, (sg, zs, za, _, _), st = ctx.net, ctx.pb, ctx.keep, _stream()
+        net, pb, (sg, zs, za, _, dirs), st = ctx.net, ctx.pb, ctx.keep, _stream()
         t, f, dev = pb.tier, pb.field, net.flat.device
         o = 4 if f == FIELD_TORSO else 0          # (the listener is the head's program: the head's output slots)
         ds = torch.zeros(pb.NP, 8, dtype=torch.float32, device=dev)
@@ -1077,23 +1145,39 @@ class DecoderTrainFn(torch.autograd.Function):
         check(lib.dfn_fold_bias_bwd(t, f, _ptr(net.flat), _ptr(sg), _ptr(zs), _ptr(za), _ptr(g_bias), _ptr(g_flat),
                                     _ptr(d_sig) if sg is not None else None, st), "dfn_fold_bias_bwd")
         net.deposit(g_flat, touched=_decoder_touched(net, (f,)))
-        return d_sig.reshape(ctx.sig_shape), None, None, None, None, None, None
+        d_pts = d_dirs = None
+        if any(ctx.pt_grad):
+            g = torch.empty(2, pb.NP, 3, dtype=torch.float32, device=dev)          # g_x, g_dhat of every point (padding rows included)
+            check(lib.dfn_points_grad(t, f, pb.NP, _ptr(net.flat), _ptr(pb.act), _ptr(pb.dy), _ptr(g[0]), _ptr(g[1]), st), "dfn_points_grad")
+            if ctx.pt_grad[0]:
+                d_pts = g[0, :pb.n]
+            if ctx.pt_grad[1]:
+                # d / |d|: (I - dhat dhat^T) / |d| applied to dL/d dhat
+                d = dirs.detach()
+                nrm = torch.linalg.vector_norm(d, dim=-1, keepdim=True)
+                dh, gd = d / nrm, g[1, :pb.n]
+                d_dirs = (gd - dh * (dh * gd).sum(-1, keepdim=True)) / nrm
+        return d_sig.reshape(ctx.sig_shape), None, None, d_pts, d_dirs, None, None
 
 
 def decoder_train(dec, field, p_in, ray_d, z_shape, z_app, signal, tier="f32"):
     """Decoder.forward(p_in [B,N,3], ray_d [B,N,3], ...) under autograd, in HIP: -> feat [B,N,3], sigma [B,N].
     field: 0 head, 1 torso, 2 listener (`signal` None: the head's program on fc_in_listener / fc_p_skips_listener,
-    decoder.py:306-307, 322-323).  Gradients flow to the decoder's parameters (deposited into .grad) and to `signal`."""
+    decoder.py:306-307, 322-323).  Gradients flow to the decoder's parameters (deposited into .grad), to `signal`, and - f32 tier -
+    to p_in and ray_d when they require grad (in the 16-bit tier they stay constants)."""
     if field not in (FIELD_HEAD, FIELD_TORSO, FIELD_LISTENER):
         raise ValueError(f"decoder_train: field {field}")
     if not dec.hip_supported():
         raise NotImplementedError("the HIP path supports the scripts/test_obama.sh decoder configuration only")
     t = TIERS["bf16" if tier in ("f16", 2) else tier]
+    # point / direction gradients run in the f32 tier; in the 16-bit tier p_in and ray_d are constants, as they always were
+    want_grad = t == 0 and torch.is_grad_enabled() and (p_in.requires_grad or ray_d.requires_grad)
     net = _FlatNet.of(dec)
     net.refresh()
     dev = net.flat.device
-    pts = p_in.detach().reshape(-1, 3).to(dev, torch.float32).contiguous()
-    dirs = ray_d.detach().reshape(-1, 3).to(dev, torch.float32).contiguous()
+    # (points that require grad stay in the graph: DecoderTrainFn returns their gradient; otherwise constants, as always)
+    pts = (p_in if want_grad else p_in.detach()).reshape(-1, 3).to(dev, torch.float32).contiguous()
+    dirs = (ray_d if want_grad else ray_d.detach()).reshape(-1, 3).to(dev, torch.float32).contiguous()
     n = pts.shape[0]
     # a fresh set of buffers per call: several forwards may be alive before their backwards run (head, then torso)
     pb = _PointBuffers(t, field, n, dev)

@@ -72,7 +72,9 @@ const char* dfn_last_error(void);
  * + dfn_render_z_fwd, dfn_render_z_fwd_u8 (the fused renderer at caller-supplied sample depths, 32 ... 192 per ray) and dfn_fine_depths
  * (the fused fine sampler + merge on its own); inference tiers, both widths; nothing else changes, the version string stays;
  * + dfn_train_rays_fwd, dfn_train_rays_fwd_hier, dfn_composite_bwd_rays_z, dfn_composite_bwd_hier_rays_z (the fused training step on
- * caller-supplied rays; f32 and bf16; nothing else changes, the version string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * caller-supplied rays; f32 and bf16; nothing else changes, the version string stays); + dfn_composite_bwd_rays_zg,
+ * dfn_composite_bwd_hier_rays_zg, dfn_points_grad, dfn_rays_grad (ray gradients of that step; f32; nothing else changes, the version
+ * string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -439,6 +441,43 @@ int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, cons
                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
                                   void* stream);
+/* Ray gradients of that step (DFN_TIER_F32 only): dL/d rays [ray_count, 12], in the layout of `rays`.  In the reference p_in and ray_d are
+ * ordinary tensors going into Decoder.forward and the compositing code (DEC:277-349, MAIN:146-179, 855-899), so torch autograd
+ * reaches a learnable pose or lens model through them; here the step's backward stops at the first layer's pre-activation gradient,
+ * and these four entry points carry it on.  bounds, z_all and the fine depths stay constants (no gradient), as in the step itself.
+ *
+ * The two compositing backwards with the gradient of the ray NORMS (MAIN:169-179: dists = dz * |d|, the only way a direction's length
+ * reaches an image): the _rays_z signatures plus
+ *   d_norm  f32 [ray_count, 2], out: dL/d|d_head| (the head image measures its distances with |d_head|) and dL/d|d_torso| (the composite
+ *           with |d_torso|) = (1 / |d|) * sum_s dL/d(s_s) * (s_s + 1e-6), s_s the effective density of the image at sample s.
+ * dsamples and the zero fill are bit for bit those of the _rays_z forms; the refusals are theirs, plus d_norm == NULL. */
+int dfn_composite_bwd_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                              const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                              long zero_floats, float* d_norm, void* stream);
+int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                   float* d_norm, void* stream);
+/* dL/d(point) and dL/d(unit view direction) of every evaluated point of one field, after dfn_mlp_bwd has written dy_T (on the stream
+ * that owns it): differentiates the positional encodings (DEC:257-275) and the layers that read them (DEC:291-311, 321-325; the
+ * deformation field DEC:109-134 with its residual DEC:299; the view layer DEC:337-340).
+ *   field   0 head, 1 torso, 2 listener;  NP a multiple of 32 (the NP of dfn_mlp_bwd)
+ *   params  the flat f32 parameter vector (the input layers' weights are read from it, not from the packed streams)
+ *   act_T / dy_T  the recorded activations and pre-activation gradients of the field, f32 tier layout ([NP/32][rows][32])
+ *   g_x, g_dhat   f32 [NP, 3], out, in evaluation order: dL/d p_in, and dL/d(ray_d / |ray_d|)
+ * Fixed summation order, no atomics: bit-reproducible.  DFN_E_ARG before any device work: a tier other than DFN_TIER_F32 (the message
+ * names the f32 tier), DFN_WIDTH_128, a bad field, a NULL pointer, NP <= 0 or not a multiple of 32. */
+int dfn_points_grad(int tier, int field, long NP, const float* params, const void* act_T, const void* dy_T, float* g_x, float* g_dhat,
+                    void* stream);
+/* ... summed to the rays (MAIN:638-641: p = o + d * z; DEC:337: d / |d|): per field g_o = sum_j g_x_j and
+ * g_d = sum_j z_j * g_x_j + (I - dhat dhat^T) / |d| * sum_j g_dhat_j + g_|d| * dhat, with z_j the depth of evaluated point j (coarse step:
+ * from that ray's bounds, or frame.z_near / z_far when bounds == NULL; hierarchical step: z_all[r, ranks[r, j]]) and g_|d| = d_norm.
+ * Frame fields used: ray_count, n_coarse, n_fine, z_near / z_far.  d_rays f32 [ray_count, 12], out.  The refusals of dfn_points_grad's
+ * tier argument; NULL pointers; sample counts other than 32 / 64 / 128 coarse or 64 + 64 | 128; z_all / ranks missing in the
+ * hierarchical step. */
+int dfn_rays_grad(int tier, const DfnFrame* frame, const float* rays, const float* bounds, const float* z_all, const uint8_t* ranks,
+                  const float* g_x_head, const float* g_dhat_head, const float* g_x_torso, const float* g_dhat_torso, const float* d_norm,
+                  float* d_rays, void* stream);
 int dfn_mlp_bwd(int tier, int field, const void* packed_T, const float* samples, const float* dsamples,
                 const uint32_t* masks, long NP, void* dy_T, void* stream);
 /* The weight-gradient plan of `field` (0 head, 1 torso), for tests and tools: what == 0 -> the GEMM list, 6 int32 per GEMM

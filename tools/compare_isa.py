@@ -9,10 +9,18 @@ paths and compiler remarks) and every line that names the __hip_cuid_<hash> symb
 contents).  Any other .s file of that suffix found in the directories (a unit compiled device-only to assembly by hand:
 hipcc --cuda-device-only -S -o <dir>/<unit>-hip-amdgcn-amd-amdhsa-gfx950.s) is compared the same way.
 
-Prints one line per unit and the differing ones again at the end; exit status 0 when every unit is identical, 1 otherwise."""
+Prints one line per unit and the differing ones again at the end; exit status 0 when every unit is identical, 1 otherwise.
+
+    tools/compare_isa.py --per-kernel <build dir A> <build dir B>
+
+For a change that ADDS kernels to a unit (the unit's file then differs by construction) or gives a kernel template one more
+argument (the mangled names change): every kernel of A must have a kernel with the same instruction stream in B.  A kernel's body is
+the text between its label and its .Lfunc_end; mangled names, the numbers of local labels (they count the unit's functions) and
+trailing comments are dropped before the comparison.  Exit status 0 when every kernel of every unit of A is found in B."""
 import difflib
 import glob
 import os
+import re
 import sys
 
 SUFFIX = "-hip-amdgcn-amd-amdhsa-gfx950.s"
@@ -26,6 +34,47 @@ def kept_isa(path):
             continue
         lines.append(s)
     return lines
+
+
+def kernel_bodies(path):
+    """label -> normalised lines of every function of an assembly file"""
+    out, cur, closed = {}, None, set()
+    for line in open(path, errors="replace"):
+        s = line.split(";")[0].strip()
+        if not s or s.startswith("//") or "__hip_cuid" in s:
+            continue
+        m = re.match(r"^(_Z\w+):", s)
+        if m and cur is None:
+            cur = m.group(1)
+            out[cur] = []
+        elif cur is not None:
+            if s.startswith(".Lfunc_end"):
+                closed.add(cur)
+                cur = None
+            else:
+                out[cur].append(re.sub(r"\.L(BB|tmp|func_begin|JTI)\d+", r".L\1", re.sub(r"_Z\w+", "SYM", s)))
+    return {k: v for k, v in out.items() if k in closed}          # (a data symbol has a label and no .Lfunc_end)
+
+
+def per_kernel(a, b):
+    ua, ub = units(a), units(b)
+    missing = 0
+    for u in sorted(ua):
+        if u not in ub:
+            print("%-32s only in %s" % (u, a))
+            missing += 1
+            continue
+        ka, kb = kernel_bodies(ua[u]), kernel_bodies(ub[u])
+        have = {}
+        for name, body in kb.items():
+            have.setdefault("\n".join(body), []).append(name)
+        lost = [name for name, body in ka.items() if "\n".join(body) not in have]
+        renamed = sum(1 for name, body in ka.items() if "\n".join(body) in have and name not in have["\n".join(body)])
+        print("%-32s %d kernels, %d with an identical body in B (%d under another name), %d more kernels in B%s" %
+              (u, len(ka), len(ka) - len(lost), renamed, len(kb) - len(ka), "; DIFFERENT: " + " ".join(lost) if lost else ""))
+        missing += len(lost)
+    print("%d units, %d kernels of A without an identical body in B" % (len(ua), missing))
+    return 1 if missing else 0
 
 
 def units(d):
@@ -55,6 +104,8 @@ def main(a, b):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--per-kernel":
+        sys.exit(per_kernel(sys.argv[2], sys.argv[3]))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))
