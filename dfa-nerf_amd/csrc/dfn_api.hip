@@ -1288,7 +1288,7 @@ int dfn_encode_signal_keep(const float* aud_params, const float* exp_params, con
     if (!keep) return fail(DFN_E_ARG, "dfn_encode_signal_keep: keep is NULL");
     return encode_signal_impl(aud_params, exp_params, att_params, auds, exps, n_total, frame_id, 1, smo_size, out, keep, stream);
 }
-long dfn_encode_signal_keep_floats(void) { return SIG_KEEP_FLOATS; }
+long dfn_encode_signal_keep_floats(void) { return SigKeep::TOTAL; }
 
 int dfn_encode_signal_torso(const float* att_params, const float* poses, int pose_stride, int n_total,
                             const int32_t* frame_ids, int n_frames, int smo_size, float* out, void* stream) {

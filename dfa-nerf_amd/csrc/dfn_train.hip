@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "dfn_bwd_kernel.h"
+#include "dfn_launch.h"
 
 namespace dfn {
 
@@ -552,7 +553,6 @@ hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier
 // sin (c = 0) / cos (c = 1) of c_o x_a / 2, so g_x[a] = sum_o (c_o / 2) (G_sin cos - G_cos sin).
 // Order of every sum: the MFMA chain runs over k ascending, term after term as listed; a lane adds its 16 accumulator rows per tile in
 // register order (tile 0, then 1), then lane n + 32 is added to lane n.  No atomics: one writer per output.
-template <typename K> static hipError_t lds_attr_once(K kernel, int bytes, bool (&done)[64]);     // (below, with the weight gradients)
 constexpr int PG_THREADS = 512, PG_WAVES = PG_THREADS / 64;
 template <bool TORSO> struct PGShape {
     static constexpr int K = TORSO ? DH : HID;                  // rows of every weight slice that meets the encoding
@@ -667,12 +667,10 @@ hipError_t launch_points_grad(int field, const PointsGradArgs& A, hipStream_t st
     const int blocks = (int)(want < cap ? want : cap);
     hipError_t e;
     if (torso) {
-        static bool done[64] = {};
-        if ((e = lds_attr_once(points_grad_kernel<true>, lds, done)) != hipSuccess) return e;
+        if ((e = lds_limit<points_grad_kernel<true>>(lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(points_grad_kernel<true>, dim3(blocks), dim3(PG_THREADS), lds, st, A);
     } else {
-        static bool done[64] = {};
-        if ((e = lds_attr_once(points_grad_kernel<false>, lds, done)) != hipSuccess) return e;
+        if ((e = lds_limit<points_grad_kernel<false>>(lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(points_grad_kernel<false>, dim3(blocks), dim3(PG_THREADS), lds, st, A);
     }
     return hipGetLastError();
@@ -958,19 +956,6 @@ __global__ __launch_bounds__(256) void wgrad_full_kernel(const WOp* ops, const i
                                               dbias, n_bias, (lds_char*)wf1_smem);
 }
 
-// hipFuncSetAttribute once per (kernel, device): a second device of the process needs it too
-template <typename K> static hipError_t lds_attr_once(K kernel, int bytes, bool (&done)[64]) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return hipSuccess;
-}
-
 hipError_t launch_wgrad(int tier, int field, const WOp* ops_dev, const int* full_ops_dev, int n_full, const WNItem* nitems_dev,
                         int n_nitems, const void* dy_T, const void* act_T, long NP, int ksplit, float* C, long c_stride,
                         const int* e_of, float* dbias, int n_bias, hipStream_t st) {
@@ -981,15 +966,13 @@ hipError_t launch_wgrad(int tier, int field, const WOp* ops_dev, const int* full
     hipError_t e;
     if (n_full > 0) {           // the 256 x 256 GEMMs (8 of a field's GEMMs, 89 % of its FLOPs): one workgroup per (GEMM, slice)
         constexpr int lds = 2 * (8 + 8) * 2 * 1024;             // two stages of 16 points
-        static bool done[64] = {};
-        if ((e = lds_attr_once(wgrad_full_kernel, lds, done)) != hipSuccess) return e;
+        if ((e = lds_limit<wgrad_full_kernel>(lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(wgrad_full_kernel, dim3(n_full * ksplit), dim3(256), lds, st, ops_dev, full_ops_dev, dy, ac, NP / 32,
                            g_rows, a_rows, ksplit, C, c_stride, e_of, dbias, n_bias);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (n_nitems > 0) {         // everything else, side by side in one launch
-        static bool done[64] = {};
-        if ((e = lds_attr_once(wgrad_narrow_kernel, WN_LDS_BYTES, done)) != hipSuccess) return e;
+        if ((e = lds_limit<wgrad_narrow_kernel>(WN_LDS_BYTES)) != hipSuccess) return e;
         hipLaunchKernelGGL(wgrad_narrow_kernel, dim3(n_nitems), dim3(256), WN_LDS_BYTES, st, ops_dev, nitems_dev, dy, ac, NP / 32, g_rows,
                            a_rows, ksplit, C, c_stride, e_of, dbias, n_bias);
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1105,12 +1088,8 @@ __global__ __launch_bounds__(SP_THREADS) void sample_pixels_kernel(int H, int W,
 hipError_t launch_sample_pixels(int H, int W, int n, int rect_num, const int* rect, unsigned long long seed,
                                 unsigned long long counter, int* out, int* status, hipStream_t st) {
     constexpr int lds = (SP_TABLE + SP_M + 2 * SP_THREADS) * 4;
-    static bool done = false;
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)sample_pixels_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
+    hipError_t e = lds_limit<sample_pixels_kernel>(lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sample_pixels_kernel, dim3(1), dim3(SP_THREADS), lds, st, H, W, n, rect_num, rect, seed, counter, out,
                        status);
     return hipGetLastError();
