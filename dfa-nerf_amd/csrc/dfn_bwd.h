@@ -35,14 +35,12 @@ struct BwdIO {
 
 // g (accumulators of a tile pair) *= ReLU mask bits (word = pair index)
 DFN_DEV void apply_mask(f32x16 (&acc)[2], unsigned bits) {
-#ifndef DFN_NOMASK
 #pragma unroll
     for (int b = 0; b < 32; ++b) {      // bit b sign-extended to a word (v_bfe_i32), ANDed onto the value: 2 ops per value
         const unsigned keep = (unsigned)__builtin_amdgcn_sbfe((int)bits, mask_pos(b), 1);
         const float x = acc[b >> 4][b & 15];          // a scalar copy: __builtin_bit_cast of a vector ELEMENT miscompiles
         acc[b >> 4][b & 15] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & keep);
     }
-#endif
 }
 // 16-bit tiers: the same on the PACKED operand words of the pair (tiles t0, t0 + 1 of v).  Word j = 8 g + 4 h + e of the pair
 // holds values 2 j (low half) and 2 j + 1 (high half), whose bits sit at j and 16 + j of the mask dword (mask_pos): shifting
@@ -53,7 +51,6 @@ DFN_DEV void apply_mask(f32x16 (&acc)[2], unsigned bits) {
 template <int TIER, int NT>
 DFN_DEV void apply_mask_packed(Vec<TIER, NT>& v, int t0, unsigned bits) {
     static_assert(tier_is16(TIER), "packed operand words");
-#ifndef DFN_NOMASK
     typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int gh = 0; gh < 4; ++gh) {             // register 2 (t0 + g) + h of v, g = gh >> 1, h = gh & 1: words 4 gh .. 4 gh + 3
@@ -74,30 +71,15 @@ DFN_DEV void apply_mask_packed(Vec<TIER, NT>& v, int t0, unsigned bits) {
         const u32x4_ r = {w[0], w[1], w[2], w[3]};
         v.u[2 * t0 + gh] = __builtin_bit_cast(typename std::remove_reference<decltype(v.u[0])>::type, r);
     }
-#endif
 }
-#ifndef DFN_PACKED_MASK
-#define DFN_PACKED_MASK 1
-#endif
 DFN_DEV unsigned mask_word(const BwdIO& io, int dword, int lane) {
-#ifdef DFN_EXP_CONSTMASK      // timing experiment (wrong results): no mask LOADS (a value the compiler cannot fold)
-    return (unsigned)io.mask_dwords * 0x9E3779B1u + (unsigned)(dword * 64 + lane) * 0x85EBCA6Bu;
-#endif
     const gchar* mb = uniform_ptr(io.masks + ((long)io.pass * io.mask_dwords + dword) * 64);
     return *(const __attribute__((address_space(1))) unsigned*)(mb + (unsigned)lane * 4u);
 }
 
 template <int TIER, int NT, class CT>
 DFN_DEV void put(const BwdIO& io, int row0, const Vec<TIER, NT>& v, const CT& c) {
-#ifndef DFN_NOPUT
-#ifdef DFN_PUT_EIGHTH     // timing experiment (wrong results): one tile in eight is stored - the chain stays alive, 7/8 of the stores go
-    store_tiles_T<TIER, NT>(io.dy_T, io.rows, io.pass, row0, v, 0, 1, c);
-#elif defined(DFN_PUT_SMALL)      // timing experiment (wrong results): every workgroup writes the same 8 tiles - the stores are issued, HBM is not
-    store_vec_T<TIER, NT>(io.dy_T, io.rows, io.pass & 7, row0, v, c);
-#else
     store_vec_T<TIER, NT>(io.dy_T, io.rows, io.pass, row0, v, c);
-#endif
-#endif
 }
 
 // Pin a finished vector where the source computes it.  The torso kernel's skip-path product (fc_p_skips_torso^T x g4) is
@@ -125,24 +107,17 @@ template <int TIER, int NT> DFN_DEV void pin_vec(Vec<TIER, NT>& v) {
     }
 }
 
-// DFN_PUT_SPREAD: how the dy_T stores of a layer's INPUT vector (the previous layer's finished output, alive as this
-// layer's B operand anyway) are issued.  0: one burst in front of the layer, all eight waves of the workgroup at once.
-// 1: spread between the MFMAs of the whole layer (PutSide: one 16-byte MX-fp8 tile store every T / NTB k-steps).
+// The dy_T stores of a layer's INPUT vector (the previous layer's finished output, alive as this layer's B operand anyway) are
+// spread between the MFMAs of the whole layer (PutSide: one 16-byte MX-fp8 tile store every T / NTB k-steps), not issued as one
+// burst in front of the layer, all eight waves of the workgroup at once.  (The same in the f32 tier, one value per store - one
+// wave per SIMD: a burst of 128 store instructions in front of a layer stops the wave, and with it the matrix pipe, until the
+// memory queue has drained.)
 // History (bf16 recording, round 2): spreading 64 word stores per vector bought 5 % (head 225 -> 213 us); with one tile in
 // eight stored the head kernel took 139 us - the other 75-85 us were the 0.69 GB of stores.  Round 3 (MX-fp8, point-major
 // blocks: 8 store instructions and half the bytes per vector): head 182 us, of which the store instructions 24, the block
 // amax 10, the ReLU mask application 8; without any recording 133 us (ablation builds, tools/time_dx.py).  NOT the cause
 // (each ablated, +-3 %): the vmcnt wait of the slab hand-over (vmcnt(63)), the ReLU mask loads, the depth of the fragment
 // prefetch (compiler-sunk ds_reads pinned by sched_barrier), the instruction cache (0.3 % misses).
-#ifndef DFN_PUT_SPREAD
-#define DFN_PUT_SPREAD 1
-#endif
-#ifndef DFN_TORSO_G4_SPREAD
-#define DFN_TORSO_G4_SPREAD 1
-#endif
-#ifndef DFN_TORSO_DY0_SPREAD
-#define DFN_TORSO_DY0_SPREAD 1
-#endif
 // (MX-fp8, dfn_mlp.h: the vector's NTB 16-byte tile stores are spread evenly over the consuming layer's T = OT / 2 x KU
 // k-steps; the scales of its tile pairs are found in front of the layer)
 template <int TIER, int NTB, int KU, int T, class CT> struct PutSide {
@@ -153,22 +128,18 @@ template <int TIER, int NTB, int KU, int T, class CT> struct PutSide {
     const Q8* qs;                   // scale of tile pair p (NTB == 1: of the one tile)
     static constexpr int STRIDE = T >= NTB ? T / NTB : 1, PER = T >= NTB ? 1 : (NTB + T - 1) / T;      // k-steps per tile / tiles per k-step
     DFN_DEV void tile(int t) const {
-#ifndef DFN_NOPUT
         if constexpr (TIER == TIER_BF16) {
             if (t < NTB) store_tile8<NTB>(io.dy_T, io.rows, io.pass, row0, v, t, 0, qs[t >> 1], c);
         }
-#endif
     }
     DFN_DEV void operator()(int ku) const {
         if (row0 < 0) return;
         const int s = tg * KU + ku;
         if constexpr (TIER == TIER_F32) {       // one value per store instruction: the vector's 16 NTB values over the layer's T k-steps
-#ifndef DFN_NOPUT
             constexpr int N = 16 * NTB, PER32 = (N + T - 1) / T;
 #pragma unroll
             for (int w = 0; w < PER32; ++w)
                 if (s * PER32 + w < N) store_val_T32(io.dy_T, io.rows, io.pass, row0, s * PER32 + w, v.v[s * PER32 + w], c);
-#endif
         } else if constexpr (T >= NTB) {
             if (s % STRIDE == 0) tile(s / STRIDE);
         } else {
@@ -190,24 +161,13 @@ DFN_DEV void put_scales(const BwdIO& io, int row0, const Vec<TIER, NTB>& v, Q8 (
         }
     }
 }
-// DFN_PUT32_SPREAD: the same for the f32 tier (one wave per SIMD: a burst of 128 store instructions in front of a layer stops
-// the wave, and with it the matrix pipe, until the memory queue has drained)
-#ifndef DFN_PUT32_SPREAD
-#define DFN_PUT32_SPREAD 1
-#endif
-template <int TIER> constexpr bool put_spread() {
-    return (TIER == TIER_BF16 && DFN_PUT_SPREAD != 0) || (TIER == TIER_F32 && DFN_PUT32_SPREAD != 0);
-}
 
 // out[OT tiles] = (W^T x in) [* mask]; mask_dword0 < 0: no mask.  put_row >= 0: `in` is written to rows put_row.. of dy_T
 // on the way (PutSide)
 template <int TIER, int OT, int KU, int NTB, class CT>
 DFN_DEV void bwd_layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, int mask_dword0, const BwdIO& io, int& f,
                        Fetch<TIER>& fe, Stream& s, const CT& c, int put_row = -1) {
-    if constexpr (!put_spread<TIER>()) {
-        if (put_row >= 0) put<TIER, NTB>(io, put_row, in, c);
-        put_row = -1;
-    }
+    static_assert(TIER == TIER_BF16 || TIER == TIER_F32, "PutSide stores the training tiers' dy_T formats");
     Q8 qs[(NTB + 1) / 2];
     put_scales<TIER, NTB>(io, put_row, in, qs, c);
 #pragma unroll
@@ -224,7 +184,7 @@ DFN_DEV void bwd_layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, int mask_dw
         asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));
         const unsigned long long q1 = __builtin_readcyclecounter();
 #endif
-        if constexpr (tier_is16(TIER) && DFN_PACKED_MASK) {
+        if constexpr (tier_is16(TIER)) {
             acc_to_vec<TIER, 2, OT, false>(acc, out, 2 * tg);
             if (mask_dword0 >= 0) apply_mask_packed<TIER, OT>(out, 2 * tg, mask_word(io, mask_dword0 + tg, c.lane));
         } else {
@@ -244,10 +204,7 @@ template <int TIER, int OT, int KU1, int NTB1, int KU2, int NTB2, class CT>
 DFN_DEV void bwd_layer2(Vec<TIER, OT>& out, const Vec<TIER, NTB1>& in1, const Vec<TIER, NTB2>& in2,
                         int mask_dword0, const BwdIO& io, int& f, Fetch<TIER>& fe, Stream& s, const CT& c,
                         int put_row1 = -1) {
-    if constexpr (!put_spread<TIER>()) {
-        if (put_row1 >= 0) put<TIER, NTB1>(io, put_row1, in1, c);
-        put_row1 = -1;
-    }
+    static_assert(TIER == TIER_BF16 || TIER == TIER_F32, "PutSide stores the training tiers' dy_T formats");
     Q8 qs[(NTB1 + 1) / 2];
     put_scales<TIER, NTB1>(io, put_row1, in1, qs, c);
 #pragma unroll
@@ -258,7 +215,7 @@ DFN_DEV void bwd_layer2(Vec<TIER, OT>& out, const Vec<TIER, NTB1>& in1, const Ve
         gemm_group<TIER, 2, KU1, NTB1>(acc, in1, f, fe, s, c, NoHook{},
                                        PutSide<TIER, NTB1, KU1, (OT / 2) * KU1, CT>{io, in1, put_row1, tg, c, qs});
         gemm_group<TIER, 2, KU2, NTB2>(acc, in2, f, fe, s, c);
-        if constexpr (tier_is16(TIER) && DFN_PACKED_MASK) {
+        if constexpr (tier_is16(TIER)) {
             acc_to_vec<TIER, 2, OT, false>(acc, out, 2 * tg);
             if (mask_dword0 >= 0) apply_mask_packed<TIER, OT>(out, 2 * tg, mask_word(io, mask_dword0 + tg, c.lane));
         } else {
@@ -322,13 +279,8 @@ DFN_DEV void bwd_trunk(const BwdIn& in, Vec<TIER, 8>& dy0, Vec<TIER, 4>& gpd_ski
     // blocks[4]^T -> g4 = dL/d a4 (post-skip, no activation)
     bwd_layer<TIER, 8, B::KU_ACT, 8>(nxt, cur, -1, io, f, fe, s, c, g_trunk + GradMap::T_DY5);
     cur = nxt;
-#if DFN_TORSO_G4_SPREAD
     if constexpr (TORSO) bwd_layer<TIER, 4, B::KU_ACT, 8>(gpd_skip, cur, -1, io, f, fe, s, c, g_trunk + GradMap::T_G4);   // fc_p_skips_torso^T
     else put<TIER, 8>(io, g_trunk + GradMap::T_G4, cur, c);           // (masked in place next: no consumer layer to ride on)
-#else
-    put<TIER, 8>(io, g_trunk + GradMap::T_G4, cur, c);                // (masked in place below)
-    if constexpr (TORSO) bwd_layer<TIER, 4, B::KU_ACT, 8>(gpd_skip, cur, -1, io, f, fe, s, c);   // fc_p_skips_torso^T
-#endif
     if constexpr (TORSO) pin_vec(gpd_skip);
     if constexpr (TORSO && TIER == TIER_F32) park_store(c, gpd_skip);      // (read back by bwd_torso)
     // dy4 = g4 * [y4 > 0]
@@ -368,7 +320,7 @@ DFN_DEV void bwd_trunk(const BwdIn& in, Vec<TIER, 8>& dy0, Vec<TIER, 4>& gpd_ski
             cur = nxt;
         }
     }
-    if constexpr (!TORSO || !DFN_TORSO_DY0_SPREAD) put<TIER, 8>(io, g_trunk + GradMap::T_DY0, cur, c);      // torso: the caller's next layer writes dy0
+    if constexpr (!TORSO) put<TIER, 8>(io, g_trunk + GradMap::T_DY0, cur, c);      // torso: the caller's next layer writes dy0
     dy0 = cur;
 }
 
@@ -393,7 +345,7 @@ DFN_DEV void bwd_torso(const BwdIn& in, const BwdIO& io, Stream& s, const CT& c)
     bwd_trunk<TIER, true>(in, dy0, gsk, io, GradMap::S_TRUNK, RecMap::S_MTRUNK, f, fe, s, c);
     // dL/d pd = fc_in_torso^T x dy0 + (skip path)
     Vec<TIER, 4> gpd;
-    bwd_layer<TIER, 4, B::KU_ACT, 8>(gpd, dy0, -1, io, f, fe, s, c, DFN_TORSO_DY0_SPREAD ? GradMap::S_TRUNK + GradMap::T_DY0 : -1);
+    bwd_layer<TIER, 4, B::KU_ACT, 8>(gpd, dy0, -1, io, f, fe, s, c, GradMap::S_TRUNK + GradMap::T_DY0);
     if constexpr (TIER == TIER_F32) park_load(c, gsk);
 #pragma unroll
     for (int L = 0; L < 64; ++L) gpd.set(L, gpd.get(L) + gsk.get(L));

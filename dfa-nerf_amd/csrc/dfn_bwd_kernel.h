@@ -24,12 +24,9 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     lds_char* lds = (lds_char*)smem;
-#ifndef DFN_BWD_ASMF
-#define DFN_BWD_ASMF 0
-#endif
-    // LDS-DMA as asm: the ReLU mask loads must not drain the dY stores.  DFN_BWD_ASMF: the fragment reads as asm with counted
-    // waits too (16-bit tiers), like the inference kernels
-    typedef CtxT<false, (DFN_BWD_ASMF != 0), true> CtxB;
+    // LDS-DMA as asm: the ReLU mask loads must not drain the dY stores.  The fragment reads stay with the compiler (as asm with
+    // counted waits, like the inference kernels': not adopted here)
+    typedef CtxT<false, false, true> CtxB;
     const CtxB ctx = {lds, wave, lane, lane >> 5, {}};
     Stream s;
     s.base0 = s.base1 = A.wblob_T;
@@ -47,9 +44,9 @@ __global__ __launch_bounds__(TierCfg<TIER>::THREADS, TierCfg<TIER>::THREADS / 25
     io.rows = TORSO ? GradMap::S_ROWS : GradMap::H_ROWS;
     io.mask_dwords = TORSO ? RecMap::S_MDWORDS : RecMap::H_MDWORDS;
     __syncthreads();
-    // One pass per workgroup by default (gridDim = tiles / 8).  DFN_BWD_PERSIST: the launcher sizes the grid to one workgroup
-    // per compute unit and a workgroup walks tiles blockIdx, + gridDim, ... with the weight stream running on across its
-    // passes - no launch / ring-fill / drain bubble between the two rounds a compute unit runs; measured neutral.
+    // One pass per workgroup: the launcher's grid is tiles / 8 and the loop runs once.  (A grid of one workgroup per compute unit,
+    // each walking tiles blockIdx, + gridDim, ... with the weight stream running on across its passes: 213 -> 212 us (head),
+    // 237 -> 238 us (torso), the kernel is power-bound - not adopted, LABNOTES.md 7.)
     for (long t8 = blockIdx.x; t8 * C::WAVES < n_tiles; t8 += gridDim.x) {
         const long tile_raw = t8 * C::WAVES + wave;
         const long tile = tile_raw < n_tiles ? tile_raw : n_tiles - 1;     // idle waves redo the last tile (same values)
@@ -97,22 +94,7 @@ template <int TIER, bool TORSO> inline hipError_t launch_mlp_bwd_t(const MlpBwdA
         done = true;
     }
     const long n_tiles = A.NP / 32;
-    int blocks = (int)((n_tiles + C::WAVES - 1) / C::WAVES);
-#ifndef DFN_BWD_PERSIST
-#define DFN_BWD_PERSIST 0      // measured: 213 -> 212 us (head), 237 -> 238 us (torso): the kernel is power-bound (LABNOTES.md 7)
-#endif
-    if (DFN_BWD_PERSIST) {
-        static int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            hipDeviceProp_t pr;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
-            if (cus <= 0) cus = 256;
-        }
-        // one workgroup per compute unit (the ring fills its LDS), each with the same number of passes
-        const int rounds = (blocks + cus - 1) / cus;
-        blocks = (blocks + rounds - 1) / rounds;
-    }
+    const int blocks = (int)((n_tiles + C::WAVES - 1) / C::WAVES);
     hipLaunchKernelGGL((mlp_bwd_kernel<TIER, TORSO>), dim3(blocks), dim3(C::THREADS), lds, st, A);
     return hipGetLastError();
 }

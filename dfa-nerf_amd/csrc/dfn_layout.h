@@ -95,29 +95,25 @@ DFN_HD int kslot_to_slot(int tier, int u, int h, int e) {
 // of the 32x32x16 map carries (kslot_to_slot): the A operand of (tile, T, K = 32 step v) is, per lane, ONE whole 16-byte slot of
 // the packed stream - slot (half g & 1, row m16_row(i, T)) of fragment 2 v + (g >> 1) of the tile - one ds_read_b128, and the
 // stream, its plan and its byte counts are those of the bf16 tier.
-// DFN_F16_LDS_PERM = 1: the LDS-DMA lanes of this tier swap bits 3 and 4 of the slot they fetch (m16_dma_off), which puts the 16
-// slots a k-group reads for one T next to each other in LDS: 256 contiguous bytes per 16 lanes, where the stream's own order gives
-// two runs of 128 bytes, 256 bytes apart.
-#ifndef DFN_F16_LDS_PERM
-#define DFN_F16_LDS_PERM 1
-#endif
+// The LDS-DMA lanes of this tier swap bits 3 and 4 of the slot they fetch (m16_dma_off), which puts the 16 slots a k-group reads
+// for one T next to each other in LDS: 256 contiguous bytes per 16 lanes, where the stream's own order gives two runs of 128
+// bytes, 256 bytes apart (the unpermuted image, measured: LABNOTES.md "Permuted against unpermuted LDS image", profiles/mfma16_ab.txt).
 DFN_HD constexpr bool tier_m16(int tier) { return tier == TIER_F16; }
 DFN_HD constexpr int m16_row(int i, int T) { return (i & 7) + 16 * (i >> 3) + 8 * T; }
 // row (feature) within a 32-tile of element e of k-group g's operand / accumulator octet (e = 4 T + j)
 DFN_HD constexpr int m16_feat(int g, int e) { return (e & 3) + 8 * (e >> 2) + 4 * (g & 1) + 16 * (g >> 1); }
 // bytes from the slot of T0 to the slot of T1 in the LDS image of a fragment
-constexpr int M16_T_BYTES = DFN_F16_LDS_PERM ? 256 : 128;
+constexpr int M16_T_BYTES = 256;
 // byte offset inside a stream fragment that LDS-DMA lane `lane` fetches (it lands at LDS byte lane * 16 of the fragment's image)
 DFN_HD constexpr unsigned m16_dma_off(int lane) {
-    const unsigned x = (DFN_F16_LDS_PERM != 0) ? ((((unsigned)lane >> 3) ^ ((unsigned)lane >> 4)) & 1u) : 0u;
+    const unsigned x = (((unsigned)lane >> 3) ^ ((unsigned)lane >> 4)) & 1u;
     return ((unsigned)lane ^ (x * 0x18u)) * 16u;
 }
 // this lane's LDS byte offset, from the image of the first fragment of a quad (G = 2 tiles per k-unit: fragments [k-unit][tile]) or
 // pair (G = 1) of stream fragments, of its T0 slot of tile 0; tile 1: + FRAG_BYTES, T1: + M16_T_BYTES
 DFN_HD constexpr unsigned m16_lane_off(int lane, int G) {
     const unsigned i = lane & 15, g = (unsigned)lane >> 4;
-    const unsigned slot = (DFN_F16_LDS_PERM != 0) ? i : (i & 7) + 16 * (i >> 3);
-    return (g >> 1) * (unsigned)(G * FRAG_BYTES) + (g & 1) * 512u + slot * 16u;
+    return (g >> 1) * (unsigned)(G * FRAG_BYTES) + (g & 1) * 512u + i * 16u;
 }
 // Read `pos` (= fragment index within the 32-fragment slab: one read per stream fragment, in stream order) of a G-tile group: the
 // byte offset, from the slab's image + m16_lane_off(lane, G), of the slot the lane reads.  G = 2: reads 4 q .. 4 q + 3 are (tile 0, T0),

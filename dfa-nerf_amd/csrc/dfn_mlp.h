@@ -215,11 +215,7 @@ DFN_DEV void slab_advance(Stream& s, lds_char* ring, int wave, int lane, bool fi
 #ifdef DFN_TIMING
     const unsigned long long t0 = __builtin_readcyclecounter();
 #endif
-#ifdef DFN_EXP_VMCNT      // timing experiment (WRONG results: the weight slab may not have landed): what do the stores in the vmcnt queue cost?
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(DFN_EXP_VMCNT) : "memory");
-#else
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::LOADS_PER_SLAB) : "memory");
-#endif
 #ifdef DFN_TIMING
     const unsigned long long t1 = __builtin_readcyclecounter();
 #endif
@@ -268,11 +264,9 @@ struct Rec {
 template <bool REC, bool ASMF = false, bool ASMD = false, bool PIPE = false, bool ACT4 = false> struct CtxT {
     static constexpr bool rec_on = REC;
     static constexpr bool act_fp4 = ACT4;            // the recorder writes act_T as MX-fp4 (dfn_mlp.h "Round 4")
-#ifndef DFN_TRAIN_ASMF      // 1: the asm fragment fetch in the recording (training forward) kernels too: 413 -> 402 us; tools/check_inflight.py
-                            // (run by build.sh on their ISA as well) proves no spill or copy touches an in-flight destination
-#define DFN_TRAIN_ASMF 1
-#endif
-    static constexpr bool asm_fetch = (ASMF || (REC && DFN_TRAIN_ASMF != 0)) && (!REC || DFN_TRAIN_ASMF != 0) && (DFN_ASM_FETCH != 0);
+    // the asm fragment fetch in the recording (training forward) kernels too: 413 -> 402 us; tools/check_inflight.py (run by
+    // build.sh on their ISA as well) proves no spill or copy touches an in-flight destination
+    static constexpr bool asm_fetch = (ASMF || REC) && DFN_ASM_FETCH != 0;
     static constexpr bool asm_dma = asm_fetch || ASMD;
     static constexpr bool pipe = PIPE && !REC;
     lds_char* ring;
@@ -405,11 +399,6 @@ template <int NT, bool NONNEG = false, bool FP4 = false> DFN_DEV Q8 q8_of_tiles(
     // amax in [2^(E-127), 2^(E-126)); scale = 2^(E-127-7): |x| / scale < 256 (e4m3 holds 448; no saturation mode needed)
     const unsigned E = a >> 7;                                   // bf16: sign(1) exponent(8) mantissa(7)
     Q8 q;
-#ifdef DFN_REC8_NOAMAX        // timing experiment (wrong results): a fixed scale, no amax
-    q.e8 = 120u;
-    q.scale = __builtin_bit_cast(float, q.e8 << 23);
-    return q;
-#endif
     if constexpr (FP4) {
         // amax = 2^(E-127) (1 + m / 128): m <= 64 -> scale 2^(E-129), amax / scale = 4 (1 + m / 128) in [4, 6]; else 2^(E-128): (3, 4)
         const unsigned e = E + ((a & 0x7fu) > 64u ? 1u : 0u);
@@ -438,10 +427,6 @@ DFN_DEV void store_tile4(void* arr, int rows, long tile, int row0, const Vec<TIE
         o = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(o, __builtin_bit_cast(bf16x2_q, w3), q.scale, 3);
         out[k] = o;
     }
-#ifdef DFN_REC8_NOSTORE       // timing experiment (wrong results): everything but the store instruction
-    asm volatile("" ::"v"(out));
-    return;
-#endif
     gchar* ubase = uniform_ptr((char*)arr + tile * act_tile_bytes(rows, true) + (long)row0 * 16);
     const unsigned voff = (unsigned)((c.lane & 31) * 16 + c.half * 8);
     DFN_GSTORE_B64_NT(ubase, voff, (t - t_first) * 512, out);
@@ -472,10 +457,6 @@ DFN_DEV void store_tile8(void* arr, int rows, long tile, int row0, const Vec<TIE
         o = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o, __builtin_bit_cast(bf16x2_q, w_hi), q.scale, true);
         out[k] = __builtin_bit_cast(unsigned, o);
     }
-#ifdef DFN_REC8_NOSTORE       // timing experiment (wrong results): everything but the store instruction
-    asm volatile("" ::"v"(out));
-    return;
-#endif
     gchar* ubase = uniform_ptr((char*)arr + tile * rec8_tile_bytes(rows) + (long)row0 * 32);
     const unsigned voff = (unsigned)((c.lane & 31) * 32 + c.half * 16);
     DFN_GSTORE_B128_NT(ubase, voff, (t - t_first) * 1024, out);
@@ -517,9 +498,6 @@ DFN_DEV void store_tiles_T(void* arr, int rows, long tile, int row0, const Vec<T
                     }
             }
     } else {
-#ifdef DFN_REC32_NOSTORE      // timing experiment (wrong results): the f32 recorder without its store instructions
-        return;
-#endif
 #pragma unroll
         for (int L = 0; L < 16 * NT; ++L)
             if ((L >> 4) >= t0 && (L >> 4) < t0 + n) {
@@ -548,9 +526,6 @@ DFN_DEV void rec_vec(const CT& c, int row0, const Vec<TIER, NT>& v) {
 // store_tiles_T does for whole tiles, one store instruction at a time (the recorder and the dX chain spread them between MFMAs)
 template <class CT>
 DFN_DEV void store_val_T32(void* arr, int rows, long tile, int row0, int L, float x, const CT& c) {
-#ifdef DFN_REC32_NOSTORE      // timing experiment (wrong results)
-    return;
-#endif
     gchar* ubase = uniform_ptr((float*)arr + (tile * rows + row0) * 32);
     const int f = 32 * (L >> 4) + tile_feat(0, L & 15);
     const unsigned voff = (unsigned)(4 * c.half * 32 + (c.lane & 31)) * 4u;
@@ -562,33 +537,13 @@ DFN_DEV void store_val_T32(void* arr, int rows, long tile, int row0, int L, floa
 // layers: LDS latency hides behind the MFMAs of earlier fragments.  `fp` = index of the next fragment to
 // PREFETCH; both indices are compile-time after inlining/unrolling (in the runtime layer loops only their
 // slab phase matters, and one 256x256 layer is a whole number of slabs and of ring turns).
-// 1: the seven trunk layers as straight-line code (no `act = nxt` copies: 384 v_mov per pass, one in eight of the kernel's
-// non-MFMA vector instructions - the SIMD's vector issue port is what the MFMAs compete for - at +21 KB of code per MLP);
-// 0: two runtime loops of one layer body each.  (A ping-pong loop of two bodies makes hipcc spill ~60 VGPRs.)
-#ifndef DFN_TRUNK_UNROLL
-#define DFN_TRUNK_UNROLL 0
-#endif
-#ifndef DFN_PF_DEPTH
-#define DFN_PF_DEPTH 4
-#endif
-constexpr int PF_DEPTH = DFN_PF_DEPTH;
+constexpr int PF_DEPTH = 4;      // (8 / 2: -0.2 % / +1.7 % on C2, LABNOTES.md 4.5; the f16 tier's ring is one quad, gemm_group)
 template <int TIER, class CT> constexpr bool use_asm_fetch() { return tier_is16(TIER) && CT::asm_fetch; }
 // (the asm fragment READS are for the 16-bit tiers only.)  The asm DMA serves every kernel of the f32 tier (round 6; before,
 // this function answered tier_is16 whenever asm_fetch was on, and the f32 kernels got the builtin: a 64-bit vector address per
 // piece and, with "LDS DMA" in the function, s_waitcnt lgkmcnt(0) in front of the MFMAs that read LDS - f32 training forward
 // 2562 -> 2496 us, c2_f32 328.2 -> 318.7 ms = 0.921 -> 0.948 of the f32 MFMA peak, the same 138.47 dB; profiles/r06z_*).
-// DFN_F32_ASM_DMA = 0: the builtin again.
-#ifndef DFN_F32_PIN_FRAGS
-#define DFN_F32_PIN_FRAGS 1
-#endif
-// the same pin in the f16x3 tier's gemm_group (one sched_barrier per (hi, lo') fragment pair and its three MFMAs); 0 = none
-#ifndef DFN_X3_PIN_FRAGS
-#define DFN_X3_PIN_FRAGS 1
-#endif
-#ifndef DFN_F32_ASM_DMA
-#define DFN_F32_ASM_DMA 1
-#endif
-template <int TIER, class CT> constexpr bool use_asm_dma() { return tier_is16(TIER) ? CT::asm_dma : (DFN_F32_ASM_DMA != 0 || CT::asm_dma); }
+template <int TIER, class CT> constexpr bool use_asm_dma() { return !tier_is16(TIER) || CT::asm_dma; }
 
 #define DFN_FRAG_CASE(K)                                                                                      \
     case K:                                                                                                   \
@@ -720,12 +675,6 @@ template <int TIER> struct Fetch {
             else buf[slot] = *(const lds_u32x4*)(c.ring + m16_lane_off(c.lane, gl) + s.rd_off + off);
         } else if constexpr (use_asm_fetch<TIER, CT>()) frag_read(buf[slot], s.rd_vaddr, fp % SLAB_FRAGS);
         else buf[slot] = *(const lds_u32x4*)(c.ring + c.lane * 16 + s.rd_off + (fp % SLAB_FRAGS) * FRAG_BYTES);
-#ifdef DFN_EXP_DBLLDS       // experiment: what does the LDS fragment traffic cost?  read every fragment a second time
-        {                   // (same results, +100 % fragment reads; the neighbouring fragment so that the data differ)
-            const u32x4 dup = *(const volatile lds_u32x4*)(c.ring + c.lane * 16 + s.rd_off + ((fp + 1) % SLAB_FRAGS) * FRAG_BYTES);
-            asm volatile("" ::"v"(dup));
-        }
-#endif
         if (fp % GAP == GAP / 2) {                                 // one piece of the slab two ahead
             const int k = (fp % SLAB_FRAGS) / GAP;                 // compile-time
             stream_issue_piece<TIER, use_asm_dma<TIER, CT>()>(s, c.ring, c.wave, c.lane, k);
@@ -787,9 +736,6 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
                     if constexpr (ASM) {
                         if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook, left >= PF_DEPTH ? G : GN);
                     }
-#ifdef DFN_GEMM_SCHEDBAR
-                    if constexpr (!ASM) __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
-#endif
                     ++f;
                 }
                 if (G == 2) side(2 * v + g);      // (one call per stream k-unit, as in the other tiers)
@@ -798,9 +744,6 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
                 side(2 * v);
                 side(2 * v + 1);
             }
-#ifdef DFN_PIPE_SCHEDBAR
-            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     } else if constexpr (TIER == TIER_F16X3) {
         // (the register ring is PF_DEPTH fragments = two (hi, lo') pairs ahead; a depth of 8 parks 6-14 more VGPRs in AGPRs)
@@ -825,17 +768,10 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
                 acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, b.u[ku], acc[g], 0, 0, 0);
                 accx[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, b.l[ku], accx[g], 0, 0, 0);
                 accx[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, b.u[ku], accx[g], 0, 0, 0);
-#ifdef DFN_GEMM_SCHEDBAR
-                __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
-#else
                 // the f32 tier's pin: each (reads of fragments f + D, MFMAs of the pair f) group stays where the source puts it
-                if constexpr (!CT::rec_on && (DFN_X3_PIN_FRAGS != 0)) __builtin_amdgcn_sched_barrier(0);
-#endif
+                if constexpr (!CT::rec_on) __builtin_amdgcn_sched_barrier(0);
             }
             side(ku);
-#ifdef DFN_PIPE_SCHEDBAR
-            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -871,26 +807,17 @@ DFN_DEV void gemm_group(f32x16 (&acc)[G], const Vec<TIER, NTB>& b, int& f, Fetch
                 if constexpr (ASM) {      // refill the slot just consumed (the MFMA has read its operands when it issued)
                     if (TAIL < 0 || left + TAIL >= PF_DEPTH) fe.load(f % PF_DEPTH, f + PF_DEPTH, s, c, hook);
                 }
-#ifdef DFN_GEMM_SCHEDBAR
-                // compiler-scheduled fragment reads: pin every (read of fragment f + PF_DEPTH, MFMA of fragment f) pair where the
-                // source puts it.  Left alone, the machine scheduler sinks each ds_read_b128 next to the MFMA that consumes it
-                // (fewer live registers) and the LDS latency of every fragment is exposed: s_waitcnt lgkmcnt(0/1) in front of
-                // every MFMA, matrix pipe 35 % busy in the dX kernels
-                if constexpr (!ASM) __builtin_amdgcn_sched_barrier(DFN_GEMM_SCHEDBAR);
-#else
-                // f32 tier, kernels that do not record (inference, dX chain): the same pin (round 6, -DDFN_GEMM_SCHEDBAR=0 builds:
-                // c2_f32 317.8 -> 314.7 ms, dX 1230 -> 1216 us per field; the recording forward LOSES 20 us with it and stays free;
-                // profiles/r06za_*)
-                if constexpr (!ASM && TIER == TIER_F32 && !CT::rec_on && (DFN_F32_PIN_FRAGS != 0)) __builtin_amdgcn_sched_barrier(0);
-#endif
+                // f32 tier, kernels that do not record (inference, dX chain): pin every (read of fragment f + PF_DEPTH, MFMA of
+                // fragment f) pair where the source puts it.  Left alone, the machine scheduler sinks each ds_read_b128 next to the
+                // MFMA that consumes it (fewer live registers) and the LDS latency of every fragment is exposed: s_waitcnt
+                // lgkmcnt(0/1) in front of every MFMA (round 6: c2_f32 317.8 -> 314.7 ms, dX 1230 -> 1216 us per field; the recording
+                // forward LOSES 20 us with it and stays free; profiles/r06za_*).  The same pin in every compiler-scheduled kernel
+                // of the 16-bit tiers was not adopted.
+                if constexpr (!ASM && TIER == TIER_F32 && !CT::rec_on) __builtin_amdgcn_sched_barrier(0);
                 ++f;
             }
             side(ku);
-#ifdef DFN_PIPE_SCHEDBAR
-            // pin the side work of a k-step between its MFMAs and the next step's: without it the scheduler pulls the
-            // convert / ReLU units together right behind the last MFMA of their accumulators (where they wait for it)
-            if constexpr (!std::is_same<typename std::decay<SD>::type, NoSide>::value) __builtin_amdgcn_sched_barrier(0);
-#endif
+            // (a sched_barrier here, pinning the side work of a k-step between its MFMAs and the next step's, was not adopted)
         }
     }
 }
@@ -904,13 +831,6 @@ DFN_DEV float relu_(float x) { return __builtin_bit_cast(float, max(__builtin_bi
 // reads like the other tiers (the pipelined layers issue them one by one), of which two repeat an address - the compiler merges them
 template <int G, bool M16 = false>
 DFN_DEV void acc_init(f32x16 (&acc)[G], const lds_f32* bias_lds, int half) {
-#ifdef DFN_EXP_NOINIT     // timing experiment (wrong results): accumulators start at zero, no bias reads from LDS
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-    return;
-#endif
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const lds_f32x4* p = (const lds_f32x4*)(bias_lds + g * 32 + half * (M16 ? 8 : 16));
@@ -946,13 +866,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <int TIER, int G, int NT, bool RELU>
 DFN_DEV void acc_to_vec(const f32x16 (&acc)[G], Vec<TIER, NT>& v, int t0) {
-#ifdef DFN_EXP_NOEPI      // timing experiment (wrong results): what does the convert / ReLU epilogue cost?  One value per
-    {                     // tile keeps the data dependency on the accumulators alive
-#pragma unroll
-        for (int g = 0; g < G; ++g) v.set(16 * (t0 + g), acc[g][0]);
-        return;
-    }
-#endif
     if constexpr (tier_is16(TIER)) {
         typedef typename std::conditional<TIER == TIER_F16, f16x2, bf16x2>::type pk2;     // v_cvt_pk_{f16,bf16}_f32 (RNE)
         typedef typename std::conditional<TIER == TIER_F16, f16x8, bf16x8>::type pk8;
@@ -1023,9 +936,6 @@ DFN_DEV void rec_vals(const CT& c, int row0, const Vec<TIER, NT>& out, int t0) {
 DFN_HD constexpr int mask_pos(int b) { return ((b & 1) << 4) | (b >> 1); }
 template <class CT>
 DFN_DEV void rec_mask_pair(const CT& c, int mask_dword, const f32x16 (&acc)[2]) {
-#ifdef DFN_REC_NOMASK         // timing experiment (wrong results): no ReLU bits at all (f32 route)
-    return;
-#endif
     if constexpr (CT::rec_on) {
         if (mask_dword >= 0) {
             unsigned bits = 0;
@@ -1043,9 +953,6 @@ DFN_DEV void rec_mask_pair(const CT& c, int mask_dword, const f32x16 (&acc)[2]) 
 // quarter of the training forward's vector instructions were mask bits.
 template <int TIER, int NT, class CT>
 DFN_DEV void rec_mask_pair_packed(const CT& c, int mask_dword, const Vec<TIER, NT>& out, int t0) {
-#ifdef DFN_REC_NOMASK         // timing experiment (wrong results): no ReLU bits at all
-    return;
-#endif
     if constexpr (CT::rec_on && tier_is16(TIER)) {
         if (mask_dword >= 0) {
             typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
@@ -1064,10 +971,6 @@ DFN_DEV void rec_mask_pair_packed(const CT& c, int mask_dword, const Vec<TIER, N
                 }
             }
             const unsigned bits = b2[0] | b2[1];
-#ifdef DFN_REC_NOMASKSTORE    // timing experiment (wrong results): the bits, not their store
-            asm volatile("" ::"v"(bits));
-            return;
-#endif
             gchar* mb = uniform_ptr(c.rec.masks + ((long)c.rec.pass * c.rec.mask_dwords + mask_dword) * 64);
             DFN_GSTORE_B32(mb, (unsigned)c.lane * 4u, 0, bits);
         }
@@ -1139,12 +1042,8 @@ DFN_DEV void layer_pipe(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_
     acc_to_vec<TIER, 2, OT, RELU>(acc[(OT / 2 - 1) & 1], out, OT - 2);        // the last pair: not overlapped
 }
 
-// DFN_REC_SPREAD (training recorder, 16-bit tier): 1 = the scale search and the two 16-byte tile stores of tile pair tg - 1
-// go out between the MFMAs of pair tg (RecSide), like the dX chain's PutSide (dfn_bwd.h); 0 = as one burst at the next slab
-// hand-over.
-#ifndef DFN_REC_SPREAD
-#define DFN_REC_SPREAD 1
-#endif
+// Training recorder, 16-bit tier: the scale search and the two 16-byte tile stores of tile pair tg - 1 go out between the
+// MFMAs of pair tg (RecSide), like the dX chain's PutSide (dfn_bwd.h), not as one burst at the next slab hand-over.
 template <int TIER, int OT, int KU, class CT, bool NONNEG> struct RecSide {
     const CT& c;
     const Vec<TIER, OT>& out;
@@ -1165,12 +1064,9 @@ template <int TIER, int OT, int KU, class CT, bool NONNEG> struct RecSide {
     }
 };
 
-// DFN_REC32_SPREAD (training recorder, f32 tier): 1 = the 32 value stores and the ReLU bits of tile pair tg - 1 go out one by one
-// between the MFMAs of pair tg (the kernel runs ONE wave per SIMD: a burst of 32 store instructions fills the memory queue and
-// the wave - and with it the matrix pipe - waits until it drains); 0 = as one burst at the next slab hand-over.
-#ifndef DFN_REC32_SPREAD
-#define DFN_REC32_SPREAD 1
-#endif
+// Training recorder, f32 tier: the 32 value stores and the ReLU bits of tile pair tg - 1 go out one by one between the MFMAs of
+// pair tg (the kernel runs ONE wave per SIMD: as a burst of 32 store instructions at the next slab hand-over they fill the memory
+// queue and the wave - and with it the matrix pipe - waits until it drains).
 template <int OT, int KU, class CT> struct RecSide32 {
     const CT& c;
     const Vec<TIER_F32, OT>& out;
@@ -1186,17 +1082,13 @@ template <int OT, int KU, class CT> struct RecSide32 {
                 if (b < 32) {
                     const float x = out.v[32 * prev + b];
                     if (rec_row >= 0) store_val_T32(c.rec.act_T, c.rec.rows, c.rec.pass, rec_row + 64 * prev, b, x, c);
-#ifndef DFN_REC_NOMASK
                     if (mask_dword >= 0) bits |= (x > 0.f) ? (1u << mask_pos(b)) : 0u;     // (relu(x) > 0 <=> x > 0: the accumulator's bit)
-#endif
                 }
             }
-#ifndef DFN_REC_NOMASK
             if (ku == KU - 1 && mask_dword >= 0) {
                 gchar* mb = uniform_ptr(c.rec.masks + ((long)c.rec.pass * c.rec.mask_dwords + mask_dword) * 64);
                 DFN_GSTORE_B32(mb, (unsigned)c.lane * 4u, 0, bits);
             }
-#endif
         }
     }
 };
@@ -1210,7 +1102,7 @@ DFN_DEV void layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_f32* 
         layer_pipe<TIER, OT, KU, NTB, RELU>(out, in, bias, f, fe, s, c);
         return;
     }
-    if constexpr (CT::rec_on && TIER == TIER_F32 && (DFN_REC32_SPREAD != 0) && KU >= 8) {
+    if constexpr (CT::rec_on && TIER == TIER_F32 && KU >= 8) {
         unsigned bits = 0;
 #pragma unroll
         for (int tg = 0; tg < OT / 2; ++tg) {
@@ -1225,7 +1117,7 @@ DFN_DEV void layer(Vec<TIER, OT>& out, const Vec<TIER, NTB>& in, const lds_f32* 
         if (rec_row >= 0) rec_vals<TIER>(c, rec_row + 64 * (OT / 2 - 1), out, OT - 2);
         return;
     }
-    constexpr bool SPREAD = CT::rec_on && TIER == TIER_BF16 && (DFN_REC_SPREAD != 0);
+    constexpr bool SPREAD = CT::rec_on && TIER == TIER_BF16;
     bool pend = false;          // the values of pair tg - 1 wait for the next slab hand-over
 #pragma unroll
     for (int tg = 0; tg < OT / 2; ++tg) {
@@ -1457,19 +1349,17 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
     Vec<TIER, HT> nxt;
     // blocks[0..6] with the skip after blocks[3] (decoder.py:313-325), ping-ponging between the two operand vectors:
     // the trunk's output a7 ends up in `nxt`.  Every layer starts at the same slab phase f_l1 (a layer is 128 fragments,
-    // the skip adds a multiple of 32).  DFN_TRUNK_UNROLL: see below.
+    // the skip adds a multiple of 32).
     const auto blk_bias = [&](int k) { return bias + (k < 4 ? b_l1 + 256 * k : b_l5 + 256 * (k - 4)); };
-    const auto blk_row = [&](int k) { return r_trunk + RecMap::T_A0 + 256 * (k + 1); };          // output of blocks[k]
-    const auto blk_mask = [&](int k) { return m_trunk + (k < 4 ? RecMap::TM_A0 + 4 * (k + 1) : RecMap::TM_A5 + 4 * (k - 4)); };
     int f = f_l1;
     // "Every layer starts at the same slab phase" needs a layer AND the skip's extra group to be whole slabs.  In the 128-wide
     // program (HT = 4) a 16-bit layer is 32 fragments but the HEAD's skip adds 4 x KU_PE = 16: the layers behind it start at
     // phase f_l1 + 16.  That one trunk runs straight-line with the TRUE running fragment index (`f` is never reset); every other
-    // one (the torso's skip adds 32, the f32 / f16x3 tiers double everything) keeps the forms below.
+    // one (the torso's skip adds 32, the f32 / f16x3 tiers double everything) runs the loops below.
     constexpr bool SAME_PHASE = P::F_LAYER % SLAB_FRAGS == 0 && (HT * KUP * P::FS) % SLAB_FRAGS == 0;
     static_assert(SAME_PHASE || HT != 8, "the 256-wide program resets the fragment index per layer");
     static_assert(P::F_LAYER % PF_DEPTH == 0 && (HT * KUP * P::FS) % PF_DEPTH == 0, "register ring turns");
-    constexpr bool STRAIGHT = (DFN_TRUNK_UNROLL != 0) || !SAME_PHASE;
+    constexpr bool STRAIGHT = !SAME_PHASE;
     if constexpr (!SAME_PHASE) {
         static_assert(!CT::rec_on, "the 128-wide program is inference only (no recorder rows for it)");
 #define DFN_PLAIN(OUT, IN, K) layer<TIER, HT, P::KU_ACT, HT, true>(OUT, IN, blk_bias(K), f, fe, s, c)
@@ -1482,21 +1372,9 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
         DFN_PLAIN(nxt, act, 6);
 #undef DFN_PLAIN
     } else {
-#if DFN_TRUNK_UNROLL
-    // straight-line: seven layer bodies, the operand vectors alternate by name (no copies, no loop-carried vectors)
-#define DFN_PLAIN(OUT, IN, K) f = f_l1; layer<TIER, HT, P::KU_ACT, HT, true>(OUT, IN, blk_bias(K), f, fe, s, c, blk_row(K), blk_mask(K))
-    DFN_PLAIN(nxt, act, 0);
-    DFN_PLAIN(act, nxt, 1);
-    DFN_PLAIN(nxt, act, 2);
-    f = f_l1;       // blocks[3], then the skip: relu(.) + fc_z_skips(z) + fc_p_skips(p)   (decoder.py:316-325)
-    layer_skip<TIER, HT, P::KU_ACT, HT, KUP, NTP>(act, nxt, bias + b_l1 + 256 * 3, pvec, bias + b_skip, f, fe, s, c,
-                                                  r_trunk + RecMap::T_A0 + 256 * 4, m_trunk + RecMap::TM_A4R);
-    DFN_PLAIN(nxt, act, 4);
-    DFN_PLAIN(act, nxt, 5);
-    DFN_PLAIN(nxt, act, 6);
-#undef DFN_PLAIN
-#else
-    // runtime loops (one layer body each): the copy of the operand vector after every layer is the price of the small code
+    // runtime loops (one layer body each): the copy of the operand vector after every layer (384 v_mov per pass) is the price of
+    // the small code.  (The seven layers as straight-line code, no copies: +21 KB of code per MLP, not adopted; a ping-pong loop
+    // of two bodies makes hipcc spill ~60 VGPRs.)
     for (int l = 0; l < 3; ++l) {
         f = f_l1;
         layer<TIER, HT, P::KU_ACT, HT, true>(nxt, act, bias + b_l1 + 256 * l, f, fe, s, c,
@@ -1513,7 +1391,6 @@ DFN_DEV MlpOut mlp_trunk(Vec<TIER, HT>& act, const Vec<TIER, NTP>& pvec, const D
                                              r_trunk + RecMap::T_A0 + 256 * (5 + l), m_trunk + RecMap::TM_A5 + 4 * l);
         act = nxt;
     }
-#endif
     }
     // the trunk's output a7: in `nxt` after the straight-line form, in `act` after the loops; the other vector takes the
     // view layer's output

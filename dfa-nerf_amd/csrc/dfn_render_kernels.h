@@ -199,23 +199,13 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     lds_char* lds = (lds_char*)smem;
     // inference: asm fragment fetch (DFN_ASM_FETCH); training: asm LDS-DMA only.  Pipelined layers in the head-only
     // 16-bit kernel (the two-field kernel has no 32 registers to spare)
-#ifndef DFN_PIPE
-#define DFN_PIPE 1
-#endif
-#ifndef DFN_PIPE_TWO         // 1: pipelined layers in the two-field kernel too.  Round 4, measured: 256 VGPRs + 15 spilled (60 B of scratch: the
-                             // build's no-scratch check for the 16-bit inference kernels would refuse it), C3 72.39 -> 71.86 ms (-0.7 %,
-                             // interleaved, three rounds): not adopted
-#define DFN_PIPE_TWO 0
-#endif
-#ifndef DFN_PIPE_TWO_HEAD    // 1: in the two-field kernel the HEAD's passes run the pipelined layers, the torso's (whose deformation
-                             // field and skip input hold the registers the second accumulator set needs) the plain ones: 256
-                             // VGPRs, nothing spilled, the same bits; C3 70.62 -> 70.24-70.36 ms (-0.4 %, interleaved, three rounds -
-                             // the kernel sits at its power ceiling, LABNOTES.md 4.6: a better schedule is paid back in clock)
-#define DFN_PIPE_TWO_HEAD 1
-#endif
-    typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, (DFN_PIPE != 0) && TRAIN == 0 && (!TWO || DFN_PIPE_TWO != 0), TRAIN != 0 && ACT4> CtxK;      // (fused step: act_T in MX-fp4 unless ACT4 is off)
+    // The two-field kernel: the HEAD's passes run the pipelined layers, the torso's (whose deformation field and skip input hold the
+    // registers the second accumulator set needs) the plain ones: 256 VGPRs, nothing spilled, the same bits; C3 70.62 ->
+    // 70.24-70.36 ms (-0.4 %; the kernel sits at its power ceiling, LABNOTES.md 4.6: a better schedule is paid back in clock).
+    // Torso passes pipelined too: 256 VGPRs + 15 spilled (the build's no-scratch check would refuse it), C3 -0.7 %, not adopted.
+    typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, TRAIN == 0 && !TWO, TRAIN != 0 && ACT4> CtxK;      // (fused step: act_T in MX-fp4 unless ACT4 is off)
     CtxK ctx = {lds, wave, lane, tier_m16(TIER) ? m16_bias_oct(lane) : lane >> 5, {}};      // (f16: dfn_mlp.h acc_init)
-    typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, (DFN_PIPE != 0) && TRAIN == 0 && (!TWO || DFN_PIPE_TWO != 0 || DFN_PIPE_TWO_HEAD != 0), TRAIN != 0 && ACT4> CtxH;   // the head's passes
+    typedef CtxT<TRAIN != 0, TRAIN == 0, TRAIN != 0, TRAIN == 0, TRAIN != 0 && ACT4> CtxH;   // the head's passes
     constexpr bool two = TWO;
     const int NF = TRAIN == 1 ? 0 : F.n_fine;     // TRAIN == 1: the training forward is the reference's coarse renderer
     const bool hier = NF > 0;
@@ -240,9 +230,6 @@ __global__ __launch_bounds__(TierCfg<(TW & TIER_MASK)>::THREADS, TierCfg<(TW & T
     unsigned long long T_mlp = 0, T_pdf = 0;
     const unsigned long long T_start = __builtin_readcyclecounter();
     const unsigned long long R_start = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef DFN_PRIO_YOUNG      // experiment (static priority for the second-dispatched half): no effect on C2, not enabled
-    if (wave >= C::WAVES / 2) __builtin_amdgcn_s_setprio(1);
 #endif
     const bool probe = A.clock_probe && blockIdx.x == gridDim.x / 2 && wave == 0;       // wave-uniform
     unsigned long long probe_c0 = 0, probe_r0 = 0;

@@ -28,28 +28,17 @@
 namespace dfn {
 
 constexpr int WL_WAVES = 8, WL_THREADS = 64 * WL_WAVES;
-#ifndef DFN_WL_DEPTH
-#define DFN_WL_DEPTH 4
-#endif
 // Cache policy of the operand stream: every byte is read once by one workgroup -> non-temporal (measured, both fields, alone:
 // DMA stream only 339 -> 319 us, whole kernel 448 -> 438 us; sc1 / sc0 sc1: no change).  Also measured and NOT adopted: the
 // arrays laid out [row block][tile] (sequential 1-KiB streams instead of 8-KiB runs at a 77-KB stride): the same 4.4-4.5 TB/s;
 // every other piece through registers instead of LDS-DMA: the same - the stream is bound on the memory side, not by the
-// LDS-DMA path of a compute unit.  Where the kernel's time goes (both fields, alone; timing builds DFN_WL_NOMFMA / DFN_WL_NOLDS):
+// LDS-DMA path of a compute unit.  Where the kernel's time goes (both fields, alone; ablation builds, tools/exp_ablations.patch):
 // DMA stream + barriers 311 us, + the MFMAs on constant operands 386 us, + the transpose reads = the kernel, 439 us.  A
 // register-double-buffered variant (reads of pair q + 1 under the MFMAs of pair q; needs 4 waves x 128 x 128 outputs to fit
 // the registers) can at best reach the 386-us row: not built.  Built and measured out: the two waves of a SIMD out of phase
 // (waves 4-7 multiply the fragments they read for the PREVIOUS pair, then read this one's, so that one wave's transpose reads run
 // under its partner's MFMAs; no second fragment set) - 472 us instead of 444, the step 1.5 % slower.
-#ifndef DFN_WL_POL
-#define DFN_WL_POL 1
-#endif
-#if DFN_WL_POL == 1
-#define DFN_WL_POLICY " nt"
-#else
-#define DFN_WL_POLICY ""
-#endif
-constexpr int WL_DEPTH = DFN_WL_DEPTH;          // ring depth in steps
+constexpr int WL_DEPTH = 4;                     // ring depth in steps
 constexpr int WL_STEP_BYTES = 32 * 1024;        // 32 operand tiles (1 KiB each) per step at most
 constexpr int WL_PIECES = 4;                    // 1 KiB DMA pieces per wave and step at most (32 per step)
 // The E8M0 scales of a chunk of the slice (16 bytes per 32-point tile: up to 8 dY row blocks + 8 X row blocks of the GEMM)
@@ -91,7 +80,7 @@ template <int N> DFN_DEV void wl_wait_vm() { asm volatile("s_waitcnt vmcnt(%0) l
 // row sums of block 4 rg + CG; the E8M0 scales are selected by the MFMA's op_sel (byte i of the dword the lane read) instead
 // of shifted; the DMA pieces are addressed as wave-uniform SGPR base + constant lane offset.
 DFN_DEV void wl_dma(unsigned voff, const char* sbase, unsigned m0v) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" DFN_WL_POLICY ::"v"(voff), "s"(sbase), "s"(m0v) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(m0v) : "memory", "m0");
 }
 // stage the E8M0 scales of tile pairs [c0, c1) into LDS: [tile of the chunk][16] = A row blocks 0..7 | B row blocks 0..7
 DFN_DEV void wl_stage_scales(lds_char* sc_lds, const unsigned char* scA, const unsigned char* scB, long strideA, long strideB,
@@ -483,7 +472,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
     const long per = (pairs + ksplit - 1) / ksplit;
     const long p0 = ks * per, p1 = (p0 + per < pairs) ? p0 + per : pairs;      // this slice's tile PAIRS
     if (p0 >= p1) return;                                               // whole workgroup
-#ifndef DFN_WL_NOFULL
     if (o.M == 256 && o.N == 256) {                                     // (whole workgroup) the specialised path
         switch (wave >> 1) {
             case 0: wl_full<0, B4>(lds, o, dy_T, act_T, p0, p1, g_rows, a_rows, ks, C, c_stride, e_of, dbias, n_bias, wave, lane); break;
@@ -500,7 +488,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
     if (o.M == 32 && o.N == 256) { wl_static<1, 8, 1, 8, 1, B4>(WL_ARGS); return; }
     if (o.M == 64 && o.N == 64) { wl_static<2, 2, 2, 1, 4, B4>(WL_ARGS); return; }
 #undef WL_ARGS
-#endif
     const int mts = o.M / 32, nts = o.N / 32, ntl = mts + nts;          // operand tiles per 32 points
     const int pps = ntl <= 4 ? 4 : (ntl <= 8 ? 2 : 1);                  // tile pairs per step (<= 32 KiB)
     const int np = pps * 2 * ntl;                                       // DMA pieces per step, <= 32
@@ -542,7 +529,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
                 t = t < 2 * c1 ? t : 2 * c1 - 1;     // ragged last step: refetch the last tile (never multiplied)
                 const char* a = src[k] + t * stride[k];
                 const unsigned d = __builtin_amdgcn_readfirstlane(slot + dst[k]);
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" DFN_WL_POLICY ::"v"(a), "s"(d) : "memory", "m0");
+                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(a), "s"(d) : "memory", "m0");
             }
     };
 
@@ -610,9 +597,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
             const lds_char* slot = lds + rd_slot * WL_STEP_BYTES;
             rd_slot = rd_slot + 1 == WL_DEPTH ? 0u : rd_slot + 1;
             const long pp = c0 + s * pps;
-#ifdef DFN_WL_NOMFMA          // timing experiment (wrong results): the DMA stream and the barriers alone
-            if (pp >= 0) continue;
-#endif
             for (int u = 0; u < pps; ++u) {
                 if (pp + u >= c1) break;
                 // the scales this lane supplies: of the pair's first tile (kh = 0) or second tile (kh = 1)
@@ -622,11 +606,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
                 const lds_char* b0 = slot + (2 * u) * ntl * 1024 + rd;          // first tile of the pair
                 const lds_char* b1 = b0 + ntl * 1024;                           // second tile
                 i32x8 a[4], b[2];
-#ifdef DFN_WL_NOLDS          // timing experiment (wrong results): the MFMAs on constant operands, no fragment reads
-                for (int i = 0; i < 4; ++i) a[i] = ones;
-                for (int j = 0; j < 2; ++j) b[j] = ones;
-                asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]));
-#else
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (i < mt_n && (nt_n > 0 || (do_bias && i == cg))) a[i] = frag_tr8(b0 + (4 * rg + i) * 1024, b1 + (4 * rg + i) * 1024);
@@ -636,7 +615,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_mx_kernel(const WOp* ops, co
                         if constexpr (B4) b[j] = frag_tr4((kh ? b1 : b0) - rd + (mts + 2 * cg + j) * 1024 + (lane & 15) * 16 + ((lane >> 4) & 1) * 8);
                         else b[j] = frag_tr8(b0 + (mts + 2 * cg + j) * 1024, b1 + (mts + 2 * cg + j) * 1024);
                     }
-#endif
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -37,36 +37,68 @@ def test_header_symbols_exported():
     assert b"gfx950" in _lib.lib.dfn_version()
 
 
+# DFN_* macros a preprocessor conditional of csrc/ may test without being a guarded developer switch: settings of the product
+# build.  Anything else must be in csrc/dfn_devguard.h's list - a switch added without that decision fails the test below.
+PRODUCT_SETTINGS = {
+    "DFN_ASM_FETCH",            # 0: compiler-scheduled fragment fetches (build.sh, tools/check_inflight.py)
+    "DFN_DPP_ASM",              # per unit: dfn_bwd_bf16.hip sets it to 0
+    "DFN_DEV_BUILD",            # the mark itself
+    "DFN_VARIANT_TIER",         # the render variant stubs build.sh writes
+    "DFN_VARIANT_FLAGS",
+    "DFN_WGRAD_KSPLIT_F32",     # host planning constants (dfn_api.hip)
+    "DFN_WS_KSPLIT_MAX",
+}
+
+
+def _tested_macros(path):
+    """every DFN_* macro that an #if / #ifdef / #ifndef / #elif of the file tests (comments dropped, continuation lines joined)"""
+    text = re.sub(r"\\\n", " ", open(path).read())
+    found = set()
+    for ln in text.split("\n"):
+        m = re.match(r"\s*#\s*(?:ifdef|ifndef|if|elif)\b(.*)", ln)
+        if m:
+            found |= set(re.findall(r"\bDFN_\w+", m.group(1).split("//")[0]))
+    return found
+
+
 def test_developer_switches_cannot_reach_the_product_library(tmp_path):
-    """the kernels' timing / ablation switches render wrong results at full speed.  (1) the in-tree library
-    is not a developer build; (2) defining any of them without DFN_DEV_BUILD is a compile error (csrc/dfn_devguard.h);
-    (3) build.sh refuses DFN_EXTRA_FLAGS without DFN_DEV_BUILD=1 before it compiles anything."""
+    """a library built with a developer switch (instrumentation; the retired ablations rendered wrong results at
+    full speed) must not pass for the product.  (1) the in-tree library is not a developer build; (2) defining any switch of
+    csrc/dfn_devguard.h's list without DFN_DEV_BUILD is a compile error; (3) every DFN_* macro a conditional of csrc/ tests is in
+    that list or a product setting named above; (4) build.sh refuses DFN_EXTRA_FLAGS without DFN_DEV_BUILD=1 before it compiles
+    anything."""
+    import glob
     import subprocess
     assert b"DEV" not in _lib.lib.dfn_version()
+    csrc = os.path.join(ROOT, "dfa-nerf_amd", "csrc")
+    guard = open(os.path.join(csrc, "dfn_devguard.h")).read()
+    guarded = set(re.findall(r"defined\((DFN_\w+)\)", guard))
+    assert {"DFN_TIMING", "DFN_WL_TRACE"} <= guarded and not guarded & PRODUCT_SETTINGS, sorted(guarded)
     src = tmp_path / "probe.cpp"
     src.write_text('#include "dfn_layout.h"\nint main() { return dfn::SLAB_FRAGS > 0 ? 0 : 1; }\n')
-    inc = ["-I", os.path.join(ROOT, "dfa-nerf_amd", "csrc"), "-I", os.path.join(ROOT, "include")]
+    inc = ["-I", csrc, "-I", os.path.join(ROOT, "include")]
     base = ["g++", "-std=c++17", "-fsyntax-only", str(src)] + inc
     assert subprocess.run(base, capture_output=True).returncode == 0
-    for sw in ("DFN_EXP_NOEPI", "DFN_REC8_NOAMAX", "DFN_NOMASK", "DFN_TIMING", "DFN_WL_NOMFMA"):
+    for sw in sorted(guarded):
         r = subprocess.run(base + ["-D" + sw], capture_output=True, text=True)
         assert r.returncode != 0 and "DFN_DEV_BUILD" in r.stderr, (sw, r.stderr[-300:])
         assert subprocess.run(base + ["-D" + sw, "-DDFN_DEV_BUILD=1"], capture_output=True).returncode == 0, sw
-    # every switch the sources mark "wrong results" is one the guard knows
-    import glob
-    import re
-    guard = open(os.path.join(ROOT, "dfa-nerf_amd", "csrc", "dfn_devguard.h")).read()
-    marked = set()
-    for f in glob.glob(os.path.join(ROOT, "dfa-nerf_amd", "csrc", "*.h*")):
-        for ln in open(f):
-            m = re.match(r"\s*#\s*(?:ifdef|elif defined\(|if defined\()\s*(DFN_\w+).*wrong results", ln)
-            if m:
-                marked.add(m.group(1))
-    assert len(marked) >= 10 and all(f"defined({sw})" in guard for sw in marked), sorted(sw for sw in marked if f"defined({sw})" not in guard)
+    # every switch of the sources is decided: guarded, or a product setting
+    tested = {}
+    for pat in ("*.h", "*.hip", "*.cpp"):
+        for f in glob.glob(os.path.join(csrc, pat)):
+            for sw in _tested_macros(f):
+                tested.setdefault(sw, []).append(os.path.basename(f))
+    assert {"DFN_TIMING", "DFN_WL_TRACE", "DFN_ASM_FETCH"} <= set(tested), sorted(tested)      # (the scan finds what is there)
+    undecided = {sw: fs for sw, fs in tested.items() if sw not in guarded and sw not in PRODUCT_SETTINGS}
+    assert not undecided, f"neither in dfn_devguard.h nor a product setting: {undecided}"
+    lib_before = os.stat(_lib.LIB_PATH)
     r = subprocess.run(["bash", os.path.join(ROOT, "dfa-nerf_amd", "build.sh")], capture_output=True, text=True,
-                       env=dict(os.environ, DFN_EXTRA_FLAGS="-DDFN_EXP_NOEPI"), timeout=60)
+                       env=dict(os.environ, DFN_EXTRA_FLAGS="-DDFN_TIMING"), timeout=60)
     assert r.returncode == 2 and "DFN_DEV_BUILD" in r.stderr, r.stderr[-300:]
     assert b"DEV" not in _lib.lib.dfn_version() and os.path.exists(_lib.LIB_PATH)        # ... and it touched nothing
+    lib_after = os.stat(_lib.LIB_PATH)
+    assert (lib_after.st_mtime_ns, lib_after.st_size) == (lib_before.st_mtime_ns, lib_before.st_size)
 
 
 def test_error_paths_without_gpu():

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): the dX chain (dfn_mlp_bwd) of one training step alone, per field, in a loop.
-   python tools/time_dx.py [bf16|f32]      (DFN_LIB selects a variant library, e.g. a -DDFN_NOPUT build)"""
+   python tools/time_dx.py [bf16|f32]      (DFN_LIB selects a variant library, e.g. a -DDFN_NOPUT build of a tree with
+   tools/exp_ablations.patch applied: the ablation switches are no longer in the sources)"""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dfa-nerf_amd"))
