@@ -996,6 +996,71 @@ int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, con
                                   .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream},
                                  d_norm);
 }
+// ---- opacity and expected depth of the training step, and the compositing backward of a loss that reads them -----------------------
+// the checks the two entry points share: the ray source, two fields, the backward's counts, the hierarchical extras
+static int stats_source_checks(const std::string& who, const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds,
+                               const float* z_all, const uint8_t* ranks) {
+    if (!pix_index == !rays)
+        return fail(DFN_E_ARG, who + ": exactly one of pix_index / rays selects the ray source (" + (rays ? "both" : "neither") + " given)");
+    if (bounds && !rays) return fail(DFN_E_ARG, who + ": bounds are the per-ray (near, far) of caller-supplied rays (rays is NULL)");
+    if (frame->fields != 2)
+        return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2: stats holds the head image's and the composite's pair)");
+    const bool hier = frame->n_fine > 0;
+    if (hier ? (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)) : (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
+        return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, or 64 coarse + 64 or 128 fine samples");
+    if (hier && (!z_all || !ranks)) return fail(DFN_E_ARG, who + ": the hierarchical step (n_fine > 0) needs z_all and ranks");
+    return DFN_OK;
+}
+int dfn_composite_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* samples,
+                        const float* z_all, const uint8_t* ranks, float* stats, void* stream) {
+    const std::string who = "dfn_composite_stats";
+    if (!frame || !samples || !stats) return fail(DFN_E_ARG, who + ": a NULL pointer (frame, samples, stats)");
+    if (stats_source_checks(who, frame, pix_index, rays, bounds, z_all, ranks) != DFN_OK) return DFN_E_ARG;
+    if (frame->ray_count <= 0) return DFN_OK;
+    CompositeStatsArgs A{};
+    A.frame = *frame;
+    A.pix_index = pix_index;
+    A.rays = rays;
+    A.bounds = bounds;
+    A.samples = samples;
+    A.z_all = z_all;
+    A.ranks = ranks;
+    A.stats = stats;
+    return launched(launch_composite_stats(A, (hipStream_t)stream), "composite_stats_kernel");
+}
+int dfn_composite_bwd_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* bg_f32,
+                            const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
+                            const float* d_rgb_com, const float* d_stats, float* dsamples, float* zero_buf, long zero_floats, float* d_norm,
+                            void* stream) {
+    const std::string who = "dfn_composite_bwd_stats";
+    if (!frame || !samples || !d_rgb_head || !d_rgb_com || !d_stats || !dsamples)
+        return fail(DFN_E_ARG, who + ": a NULL pointer (frame, samples, d_rgb_head, d_rgb_com, d_stats, dsamples)");
+    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, who + ": no background given");
+    if (stats_source_checks(who, frame, pix_index, rays, bounds, z_all, ranks) != DFN_OK) return DFN_E_ARG;
+    if (d_norm && !rays) return fail(DFN_E_ARG, who + ": d_norm is the gradient of the norms of caller-supplied rays (rays is NULL)");
+    if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
+    if (frame->ray_count <= 0) return DFN_OK;
+    CompositeBwdStatsArgs A{};
+    A.frame = *frame;
+    A.pix_index = pix_index;
+    A.bg_f32 = bg_f32;
+    A.bg_u8 = bg_u8;
+    A.samples = samples;
+    A.d_rgb_head = d_rgb_head;
+    A.d_rgb_com = d_rgb_com;
+    A.dsamples = dsamples;
+    A.z_all = z_all;
+    A.ranks = ranks;
+    A.zero_buf = zero_buf;
+    A.zero_floats = zero_buf ? zero_floats : 0;
+    A.rays = rays;
+    A.bounds = bounds;
+    A.d_norm = d_norm;
+    A.d_stats = d_stats;
+    const bool hier = frame->n_fine > 0;
+    return launched(launch_composite_bwd_stats(A, hier, rays != nullptr, d_norm != nullptr, (hipStream_t)stream),
+                    hier ? "composite_bwd_hier_kernel(stats)" : "composite_bwd_kernel(stats)");
+}
 // the tier argument of the two ray-gradient entry points: f32 only
 static int ray_grad_tier(int tier, const char* who) {
     if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;

@@ -50,6 +50,26 @@ struct CompositeBwdRaysGArgs : CompositeBwdRaysArgs {
     float* d_norm;
 };
 
+// Opacity and expected depth of the training step (dfn_composite_stats: composite_stats_kernel) and their gradient
+// (dfn_composite_bwd_stats: the <.., STATS> instantiations of the two backward kernels).  d_stats f32 [rays][4] = dL/d(acc_head,
+// depth_head, acc_com, depth_com) travels in a block of its own behind whichever block the form has: the instantiations without it
+// keep their argument segment, and with it their instruction stream
+template <class Base> struct WithDStats : Base {
+    const float* d_stats;
+};
+typedef WithDStats<CompositeBwdRaysGArgs> CompositeBwdStatsArgs;      // what the launcher takes; each form is launched on its own slice
+// composite_stats_kernel: one block for all four forms (pixel ids | rays + bounds, coarse | hierarchical).  The background is not read
+struct CompositeStatsArgs {
+    DfnFrame frame;
+    const int* pix_index;       // pixel-id form: [rays]
+    const float* rays;          // rays form: [rays][12] ...
+    const float* bounds;        // ... and [rays][2] or null
+    const float* samples;       // [rays][S][8], evaluation order
+    const float* z_all;         // hierarchical step: [rays][S] merged depths ...
+    const unsigned char* ranks; // ... and [rays][S] ranks
+    float* stats;               // out [rays][4] = acc_head, depth_head, acc_com, depth_com
+};
+
 // points_grad_kernel (f32 tier): dL/d(point) and dL/d(unit view direction) of every evaluated point of one field, from the arrays a
 // backward leaves behind (dy_T: the pre-activation gradients, act_T: the recorded positional encodings) and the flat parameters
 struct PointsGradArgs {
@@ -82,6 +102,9 @@ hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st);
 hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st);      // n_fine in {64, 128}
 hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st);      // fields == 2; counts as the two above
 hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier, hipStream_t st);  // ... + d_norm
+hipError_t launch_composite_stats(const CompositeStatsArgs& A, hipStream_t st);                      // fields == 2; the backward's counts
+// the compositing backward of a loss that also reads the stats: on_rays / with_norm select the form (with_norm needs on_rays)
+hipError_t launch_composite_bwd_stats(const CompositeBwdStatsArgs& A, bool hier, bool on_rays, bool with_norm, hipStream_t st);
 hipError_t launch_points_grad(int field, const PointsGradArgs& A, hipStream_t st);                 // f32 tier; field 0 head, 1 torso, 2 listener
 hipError_t launch_rays_grad(const RaysGradArgs& A, hipStream_t st);
 // Split-K partials: C [ksplit][c_stride] and dbias [ksplit][n_bias], one writer per element and slice (no atomics);

@@ -63,9 +63,11 @@ __device__ __forceinline__ void composite_zero_fill(const CompositeBwdArgs& A) {
 }
 // the argument block of the compositing backward kernels: the plain block, or the rays form's longer one (dfn_train.h)
 // (DN: the ray-gradient forms, which also write d_norm - always with RAYS)
-template <bool RAYS, bool DN = false> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
-template <> struct CompositeArgsOf<true, false> { typedef CompositeBwdRaysArgs type; };
-template <> struct CompositeArgsOf<true, true> { typedef CompositeBwdRaysGArgs type; };
+// (STATS: the forms that also take d_stats - the form's own block with d_stats behind it)
+template <bool RAYS, bool DN = false, bool STATS = false> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
+template <> struct CompositeArgsOf<true, false, false> { typedef CompositeBwdRaysArgs type; };
+template <> struct CompositeArgsOf<true, true, false> { typedef CompositeBwdRaysGArgs type; };
+template <bool RAYS, bool DN> struct CompositeArgsOf<RAYS, DN, true> { typedef WithDStats<typename CompositeArgsOf<RAYS, DN, false>::type> type; };
 // sum over the wave in a fixed order: partners at XOR distance 32, 16, 8, 4, 2, 1 (oracle: wave_sum64); every lane ends with the sum
 __device__ __forceinline__ float wave_sum_xor(float v) {
 #pragma unroll
@@ -141,8 +143,11 @@ __device__ __forceinline__ void weights_bwd_n(const float (&sigma)[KL], const fl
 // RAYS: the step on caller-supplied rays - the norms from the directions of row `ray`, the depths between that ray's (near, far) when
 // bounds are given, the background of the last sample from row `ray`; everything behind the geometry is the same code
 // DN (with RAYS): also d_norm[ray] = (dL/d|d_head|, dL/d|d_torso|), the ray-gradient step's input (dfn_composite_bwd_rays_zg)
-template <int KL, bool RAYS = false, bool DN = false>
-__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN>::type A) {
+// STATS (dfn_composite_bwd_stats): the loss also reads stats = (acc_head, depth_head, acc_com, depth_com) of composite_stats_kernel,
+// acc = sum_FG w_i, depth = sum_FG w_i z_i.  q[i] IS dL/dw_i, so the stats add [i in FG] (g_acc + g_depth z_i) to q of their image and
+// nothing else: d sigma, the blend's branches, the ReLU masks and d_norm (norm_grad reads ds) follow through the code below
+template <int KL, bool RAYS = false, bool DN = false, bool STATS = false>
+__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN, STATS>::type A) {
     static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
     composite_zero_fill(A);
     const int lane = threadIdx.x & 63;
@@ -214,6 +219,18 @@ __global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN>::t
         Gh[k] = A.d_rgb_head[ray * 3 + k];
         Gc[k] = A.d_rgb_com ? A.d_rgb_com[ray * 3 + k] : 0.f;
     }
+    float gs[4] = {0.f, 0.f, 0.f, 0.f}, qs[2][KL];       // STATS: dL/d stats of this ray, and the term of each image's q
+    if constexpr (STATS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gs[j] = A.d_stats[ray * 4 + j];
+#pragma unroll
+        for (int k = 0; k < KL; ++k) {
+            const bool fg = live[k] && !(cbg && last[k]);
+            const float z = zval(live[k] ? lane * KL + k : NC - 1);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) qs[b][k] = fg ? gs[2 * b] + gs[2 * b + 1] * z : 0.f;
+        }
+    }
     float d_sg_h[KL], d_ch[KL][3], d_sg_t[KL], d_ct[KL][3];
     // ---- head-only image: s = relu(sg_h) (+1e-6 at the last sample), colour ch
     {
@@ -224,6 +241,7 @@ __global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN>::t
             s1[k] = h_is_bg[k] ? sh[k] + 1e-6f : sh[k];
             dist[k] = dz[k] * nrm[0];
             q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
+            if constexpr (STATS) q[k] += qs[0][k];
         }
         weights_bwd_n<KL>(s1, dist, q, live, lane, r);
         if constexpr (DN) {
@@ -263,6 +281,7 @@ __global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN>::t
 #pragma unroll
             for (int c = 0; c < 3; ++c) cm[c] = ch[k][c] * wh[k] + ct[k][c] * wt[k];
             q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
+            if constexpr (STATS) q[k] += qs[1][k];
             dist[k] = dz[k] * nrm[1];
         }
         weights_bwd_n<KL>(ssum, dist, q, live, lane, r);
@@ -324,8 +343,9 @@ hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st) {
 // merged depths; the fine depths are constants (no gradient through sample_pdf), so this is the same differentiation as
 // composite_bwd_kernel with run-time depths and the scans carried across a lane's K positions.
 // RAYS: as in composite_bwd_kernel - the norms and the background row only (the depths are z_all's)
-template <int K, bool RAYS = false, bool DN = false>
-__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS, DN>::type A) {
+// STATS: as in composite_bwd_kernel, with z_i = z_all
+template <int K, bool RAYS = false, bool DN = false, bool STATS = false>
+__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS, DN, STATS>::type A) {
     static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
     constexpr int S = 64 * K;
     __shared__ unsigned char inv_s[4][S];
@@ -386,6 +406,18 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
         sg_t[k] = q1.x; ct[k][0] = q1.y; ct[k][1] = q1.z; ct[k][2] = q1.w;
         if (cbg && lastp[k]) { ch[k][0] = bgc[0]; ch[k][1] = bgc[1]; ch[k][2] = bgc[2]; }
     }
+    float qs[2][K];                // STATS: the stats' term of each image's q = dL/dw
+    if constexpr (STATS) {
+        float gs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gs[j] = A.d_stats[ray * 4 + j];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float z = A.z_all[ray * S + lane * K + k];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) qs[b][k] = (cbg && lastp[k]) ? 0.f : gs[2 * b] + gs[2 * b + 1] * z;
+        }
+    }
     // weights + d/d(sigma) of one image over the merged samples: s (effective sigma), dist, q = colour . G per position
     auto image_bwd = [&](const float (&s)[K], const float (&dist)[K], const float (&q)[K], float (&w)[K], float (&ds)[K]) {
         float e[K], a[K], v[K], pre[K];
@@ -426,6 +458,7 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
             s1[k] = (cbg && lastp[k]) ? sh + 1e-6f : sh;
             dist[k] = dz[k] * nrm[0];
             q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
+            if constexpr (STATS) q[k] += qs[0][k];
         }
         image_bwd(s1, dist, q, w, ds);
         if constexpr (DN) {
@@ -463,6 +496,7 @@ __global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename 
 #pragma unroll
             for (int c = 0; c < 3; ++c) cm[c] = ch[k][c] * wh[k] + ct[k][c] * wt[k];
             q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
+            if constexpr (STATS) q[k] += qs[1][k];
         }
         image_bwd(ss, dist, q, w, ds);
         if constexpr (DN) {
@@ -536,6 +570,190 @@ hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier
         else hipLaunchKernelGGL((composite_bwd_kernel<1, true, true>), dim3(blocks), dim3(256), 0, st, A);
     }
     return hipGetLastError();
+}
+// ... and with d_stats (dfn_composite_bwd_stats): the <.., STATS> instantiation of the form, launched on the form's own block + d_stats
+template <class Base>
+static WithDStats<Base> stats_block(const CompositeBwdStatsArgs& A) {
+    WithDStats<Base> B{};
+    static_cast<Base&>(B) = static_cast<const Base&>(A);
+    B.d_stats = A.d_stats;
+    return B;
+}
+template <bool RAYS, bool DN>
+static hipError_t launch_composite_bwd_stats_t(const CompositeBwdStatsArgs& A, bool hier, hipStream_t st) {
+    const auto B = stats_block<typename CompositeArgsOf<RAYS, DN, false>::type>(A);
+    const int blocks = (A.frame.ray_count + 3) / 4;
+    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
+    if (hier) {
+        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
+        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
+    } else {
+        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
+        else hipLaunchKernelGGL((composite_bwd_kernel<1, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
+    }
+    return hipGetLastError();
+}
+static bool stats_counts_ok(const DfnFrame& F, bool hier) {
+    if (hier) return F.n_coarse == 64 && (F.n_fine == 64 || F.n_fine == 128);
+    return (F.n_coarse == 128 || F.n_coarse == 64 || F.n_coarse == 32) && F.n_fine == 0;
+}
+hipError_t launch_composite_bwd_stats(const CompositeBwdStatsArgs& A, bool hier, bool on_rays, bool with_norm, hipStream_t st) {
+    if (!A.d_stats || A.frame.fields != 2 || !stats_counts_ok(A.frame, hier) || (on_rays && !A.rays) || (with_norm && (!on_rays || !A.d_norm)))
+        return hipErrorInvalidValue;
+    if (with_norm) return launch_composite_bwd_stats_t<true, true>(A, hier, st);
+    if (on_rays) return launch_composite_bwd_stats_t<true, false>(A, hier, st);
+    return launch_composite_bwd_stats_t<false, false>(A, hier, st);
+}
+
+// ================================================================================================
+// opacity and expected depth of the training step (DESIGN.md 4 "Opacity and expected depth", on the recorded samples)
+// ================================================================================================
+// stats[ray] = (acc_head, depth_head, acc_com, depth_com): acc = sum_FG w_i, depth = sum_FG w_i z_i over the step's final samples in
+// depth order, FG = every sample but the last when concate_bg, w the head image's (|d_head|) or the composite's (|d_torso|) weights.
+// One wave per ray, four rays per workgroup.  HIER = false: the form of composite_bwd_kernel (K = KL consecutive samples per lane,
+// lanes past n_coarse idle, the depths from the linspace); HIER = true: that of composite_bwd_hier_kernel (S = 64 K merged positions
+// through the inverse of the rank map, the depths z_all).  The weights are formed with the operations of weights_bwd_n / image_bwd
+// - expf, 1 - a + 1e-10, wave_excl_prod over the lanes' local products, the coarse form carrying the product across a lane's
+// positions (T *= v), the hierarchical one as T0 * pre - and the sigma fix-ups of the last sample; the blend's denominator shapes
+// colours, not weights, and the background colour is not read.  What dfn_composite_bwd_stats differentiates is what this writes.
+// ORDER of the sums: a lane adds its K positions in index order (p = 0; p += w, or p += w * z: a product, then a sum), then
+// wave_sum_xor (partners at XOR distance 32 ... 1).  No atomics, one writer per output: two runs give the same bits.
+template <int K, bool HIER>
+__device__ __forceinline__ void stats_weights(const float (&s)[K], const float (&dist)[K], const bool (&live)[K], int lane, float (&w)[K]) {
+    float e[K], a[K], v[K], pre[K];
+    float prod = 1.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        e[k] = expf(-((fmaxf(s[k], 0.f) + 1e-6f) * dist[k]));
+        a[k] = live[k] ? 1.0f - e[k] : 0.f;
+        v[k] = live[k] ? 1.0f - a[k] + 1e-10f : 1.0f;
+        pre[k] = prod;
+        prod *= v[k];
+    }
+    float Tb = wave_excl_prod(K == 1 ? v[0] : prod, lane);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if constexpr (HIER) {
+            w[k] = a[k] * (Tb * pre[k]);
+        } else {
+            w[k] = a[k] * Tb;
+            Tb *= v[k];
+        }
+    }
+}
+template <int K, bool HIER, bool RAYS>
+__global__ __launch_bounds__(256) void composite_stats_kernel(const CompositeStatsArgs A) {
+    constexpr int S = 64 * K;
+    __shared__ unsigned char inv_s[4][HIER ? S : 4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long ray = (long)blockIdx.x * 4 + wv;
+    if (ray >= A.frame.ray_count) return;
+    const DfnFrame& F = A.frame;
+    const int NC = HIER ? S : F.n_coarse;             // samples of the ray
+    float nrm[2];
+    float nf[2] = {F.z_near, F.z_far};
+    if constexpr (RAYS) {
+        ray_row_norms(A.rays, ray, nrm);
+        if (A.bounds) {
+            nf[0] = A.bounds[ray * 2];
+            nf[1] = A.bounds[ray * 2 + 1];
+        }
+    } else {
+        // geometry (same arithmetic as the forward and the backward kernels)
+        const int pix = A.pix_index[ray];
+        const int y = pix / F.W, x = pix - y * F.W;
+        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float* P = b ? F.pose_body : F.pose;
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
+                                          __fmul_rn(-1.0f, P[4 * k + 2]));
+                acc = __fadd_rn(acc, __fmul_rn(d, d));
+            }
+            nrm[b] = sqrtf(acc);
+        }
+    }
+    unsigned char* inv = inv_s[wv];
+    if constexpr (HIER) {      // inverse of the rank map: merged position -> evaluation index
+#pragma unroll
+        for (int m = 0; m < K; ++m) inv[A.ranks[ray * S + lane + 64 * m]] = (unsigned char)(lane + 64 * m);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const float step = coarse_step(NC);
+    auto zval = [&](int i) { return coarse_depth(nf[0], nf[1], coarse_t(step, NC, i)); };
+    const bool cbg = F.concate_bg != 0;
+    bool live[K], fg[K];
+    float z[K], s1[K], ss[K], dist_h[K], dist_c[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int i = lane * K + k;
+        live[k] = i < NC;
+        const int ii = live[k] ? i : NC - 1;
+        const bool last = ii == NC - 1;
+        float dz;
+        int ev = ii;
+        if constexpr (HIER) {
+            ev = inv[ii];
+            z[k] = A.z_all[ray * S + ii];
+            dz = last ? F.last_dist : __fsub_rn(A.z_all[ray * S + ii + 1], z[k]);
+        } else {
+            z[k] = zval(ii);
+            dz = last ? F.last_dist : __fsub_rn(zval(ii + 1), z[k]);
+        }
+        const float* sm = A.samples + ((size_t)ray * NC + ev) * 8;
+        const float sh = fmaxf(sm[0], 0.f);
+        float st = fmaxf((cbg && last) ? 0.f : sm[4], 0.f);
+        if (cbg && last) st += 1e-6f;
+        s1[k] = (cbg && last) ? sh + 1e-6f : sh;
+        ss[k] = sh + st;
+        dist_h[k] = dz * nrm[0];
+        dist_c[k] = dz * nrm[1];
+        fg[k] = live[k] && !(cbg && last);
+    }
+    float out[4];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        float w[K];
+        if (b == 0) stats_weights<K, HIER>(s1, dist_h, live, lane, w);
+        else stats_weights<K, HIER>(ss, dist_c, live, lane, w);
+        float pa = 0.f, pd = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if (fg[k]) {
+                pa += w[k];
+                pd += w[k] * z[k];
+            }
+        out[2 * b] = wave_sum_xor(pa);
+        out[2 * b + 1] = wave_sum_xor(pd);
+    }
+    // (every lane holds the four sums: lanes 0 .. 3 write one each - no alignment asked of `stats`)
+    const float o = lane == 0 ? out[0] : lane == 1 ? out[1] : lane == 2 ? out[2] : out[3];
+    if (lane < 4) A.stats[ray * 4 + lane] = o;
+}
+template <bool RAYS>
+static hipError_t launch_composite_stats_t(const CompositeStatsArgs& A, hipStream_t st) {
+    const int blocks = (A.frame.ray_count + 3) / 4;
+    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
+    if (A.frame.n_fine) {
+        if (K == 2) hipLaunchKernelGGL((composite_stats_kernel<2, true, RAYS>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_stats_kernel<3, true, RAYS>), dim3(blocks), dim3(256), 0, st, A);
+    } else {
+        if (nc == 128) hipLaunchKernelGGL((composite_stats_kernel<2, false, RAYS>), dim3(blocks), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((composite_stats_kernel<1, false, RAYS>), dim3(blocks), dim3(256), 0, st, A);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_composite_stats(const CompositeStatsArgs& A, hipStream_t st) {
+    const bool hier = A.frame.n_fine != 0;
+    if (!A.samples || !A.stats || A.frame.fields != 2 || !stats_counts_ok(A.frame, hier) || (hier && (!A.z_all || !A.ranks)) ||
+        (!A.rays == !A.pix_index))
+        return hipErrorInvalidValue;
+    return A.rays ? launch_composite_stats_t<true>(A, st) : launch_composite_stats_t<false>(A, st);
 }
 
 // ================================================================================================

@@ -117,6 +117,9 @@ def _load():
         # ray gradients of that step (f32): the _rays_z forms + d_norm, the per-point and the per-ray kernel
         "dfn_composite_bwd_rays_zg": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, lg, fp, vp]),
         "dfn_composite_bwd_hier_rays_zg": (i32, [C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, vp, fp, fp, fp, fp, lg, fp, vp]),
+        # opacity / expected depth of the training step, and the compositing backward with their gradient (both ray sources, one call)
+        "dfn_composite_stats": (i32, [C.POINTER(DfnFrame), ip, fp, fp, fp, fp, vp, fp, vp]),
+        "dfn_composite_bwd_stats": (i32, [C.POINTER(DfnFrame), ip, fp, fp, fp, vp, fp, fp, vp, fp, fp, fp, fp, fp, lg, fp, vp]),
         "dfn_points_grad": (i32, [i32, i32, lg, fp, vp, vp, fp, fp, vp]),
         "dfn_rays_grad": (i32, [i32, C.POINTER(DfnFrame), fp, fp, fp, vp, fp, fp, fp, fp, fp, fp, vp]),
         "dfn_train_loss_floats": (lg, [i32]),

@@ -223,6 +223,38 @@ class FusedTrainRaysFn(torch.autograd.Function):
         return g[:5] + (ctx.d_rays, None) + g[6:]
 
 
+class FusedTrainStatsFn(torch.autograd.Function):
+    """FusedTrainFn that also returns stats [n,4] = (acc_head, depth_head, acc_com, depth_com), the per-ray opacity and expected depth
+    of the two images (render_train(want_stats=True)): dfn_composite_stats directly behind the forward on the same stream, and in the
+    backward dfn_composite_bwd_stats in place of dfn_composite_bwd[_hier]_z.  When autograd hands no gradient for stats the backward
+    issues the launches FusedTrainFn issues."""
+
+    @staticmethod
+    def forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer=None):
+        ctx.set_materialize_grads(False)        # (a None gradient for stats must stay None)
+        return _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, want_stats=True)
+
+    @staticmethod
+    def backward(ctx, d_h, d_c, d_s):
+        return _fused_backward(ctx, d_h, d_c, d_s)
+
+
+class FusedTrainRaysStatsFn(torch.autograd.Function):
+    """FusedTrainRaysFn with stats, as FusedTrainStatsFn: dL/d rays (f32 tier) includes what reaches the rays through the stats."""
+
+    @staticmethod
+    def forward(ctx, sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, defer=None):
+        ctx.set_materialize_grads(False)
+        ctx.ray_grad = bool(ctx.needs_input_grad[5])
+        return _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, None, z_shape, z_app, defer, rays=rays, bounds=bounds,
+                              want_stats=True)
+
+    @staticmethod
+    def backward(ctx, d_h, d_c, d_s):
+        g = _fused_backward(ctx, d_h, d_c, d_s)
+        return g[:5] + (ctx.d_rays, None) + g[6:]
+
+
 # the fused step's entry points: forward by (caller-supplied rays, hierarchical, loss epilogue), compositing backward by the first two
 _FWD_ENTRY = {(False, False, False): "dfn_train_fwd", (False, True, False): "dfn_train_fwd_hier",
               (False, False, True): "dfn_train_fwd_loss", (False, True, True): "dfn_train_fwd_hier_loss",
@@ -251,7 +283,9 @@ def _ray_gradient(ctx, buf, frame, stream):
     return d_rays
 
 
-def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None, rays=None, bounds=None):
+def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, defer, loss=None, rays=None, bounds=None,
+                   want_stats=False):
+    # want_stats: also return stats [n,4] (dfn_composite_stats on the recorded samples, directly behind the forward, same stream)
     # rays / bounds: the step on caller-supplied rays (FusedTrainRaysFn; no pixel ids, no loss epilogue)
     # loss: a _lib.DfnTrainLoss -> the forward's epilogue forms the step's loss and d loss / d rgb (dfn_train_fwd*_loss)
     # defer: the SignalTrainer whose _SignalFn produced both signals (their backward then picks d(signal) up on its own
@@ -294,10 +328,16 @@ def _fused_forward(ctx, sig_head, sig_torso, buf, frame, bg, pix_index, z_shape,
     buf._fwd_seq = ctx.seq = getattr(buf, "_fwd_seq", 0) + 1
     ctx.keep = (sh, stt, zs, za)
     ctx.sig_shapes = (sig_head.shape, sig_torso.shape)
+    if want_stats:
+        stats = torch.empty(n, 4, dtype=torch.float32, device=dev)
+        check(lib.dfn_composite_stats(C.byref(frame), _ptr(pix_index), _ptr(rays), _ptr(bounds), _ptr(buf.samples), _ptr(buf.z_all),
+                                      _ptr(buf.ranks), _ptr(stats), st), "dfn_composite_stats")
+        return rgb_h, rgb_c, stats
     return rgb_h, rgb_c
 
 
-def _fused_backward(ctx, d_h, d_c):
+def _fused_backward(ctx, d_h, d_c, d_s=None):
+    # d_s: dL/d stats of the stats forms (None: no gradient for them - the launches of the step without stats)
     buf, frame, bg, st = ctx.buf, ctx.frame, ctx.bg, _stream()
     if buf._fwd_seq != ctx.seq:
         raise RuntimeError("fused training step: backward of forward #%d, but forward #%d has since overwritten the "
@@ -305,6 +345,9 @@ def _fused_backward(ctx, d_h, d_c):
                            "for a second graph)" % (ctx.seq, buf._fwd_seq))
     sh, stt, zs, za = ctx.keep
     flat, dev = buf.flat, buf.flat.device
+    if d_h is None or d_c is None:          # (the stats forms do not materialise gradients: a loss on the stats alone)
+        zero = torch.zeros(buf.n_rays, 3, dtype=torch.float32, device=dev)
+        d_h, d_c = (zero if d_h is None else d_h), (zero if d_c is None else d_c)
     d_h = d_h.contiguous().float()
     d_c = d_c.contiguous().float()
     bg_f32 = bg if bg.dtype == torch.float32 else None
@@ -324,16 +367,23 @@ def _fused_backward(ctx, d_h, d_c):
     src = (_ptr(ctx.rays), _ptr(ctx.bounds)) if ctx.rays is not None else (_ptr(ctx.pix),)
     hier = (_ptr(buf.z_all), _ptr(buf.ranks)) if buf.n_fine else ()
     ray_grad = getattr(ctx, "ray_grad", False)
-    if ray_grad:
-        # the rays require grad: the same compositing backward (bit for bit) that also leaves the gradient of the two ray norms
-        name = _BWD_ZG_ENTRY[bool(buf.n_fine)]
-        if buf.d_norm is None:
-            buf.d_norm = torch.empty(buf.n_rays, 2, dtype=torch.float32, device=dev)
-        extra = (_ptr(buf.d_norm),)
+    if ray_grad and buf.d_norm is None:
+        buf.d_norm = torch.empty(buf.n_rays, 2, dtype=torch.float32, device=dev)
+    if d_s is not None:
+        # the loss reads the stats: one entry point for every form, the same launch slot (d_norm: the rays require grad)
+        d_s = d_s.contiguous().float()
+        check(lib.dfn_composite_bwd_stats(C.byref(frame), _ptr(ctx.pix), _ptr(ctx.rays), _ptr(ctx.bounds), _ptr(bg_f32), _ptr(bg_u8),
+                                          _ptr(buf.samples), _ptr(buf.z_all), _ptr(buf.ranks), _ptr(d_h), _ptr(d_c), _ptr(d_s),
+                                          _ptr(buf.dsamples), zb, zn, _ptr(buf.d_norm) if ray_grad else None, st),
+              "dfn_composite_bwd_stats")
     else:
-        name, extra = _BWD_ENTRY[ctx.rays is not None, bool(buf.n_fine)], ()
-    check(getattr(lib, name)(C.byref(frame), *src, _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples), *hier, _ptr(d_h), _ptr(d_c),
-                             _ptr(buf.dsamples), zb, zn, *extra, st), name)
+        if ray_grad:
+            # the rays require grad: the same compositing backward (bit for bit) that also leaves the gradient of the two ray norms
+            name, extra = _BWD_ZG_ENTRY[bool(buf.n_fine)], (_ptr(buf.d_norm),)
+        else:
+            name, extra = _BWD_ENTRY[ctx.rays is not None, bool(buf.n_fine)], ()
+        check(getattr(lib, name)(C.byref(frame), *src, _ptr(bg_f32), _ptr(bg_u8), _ptr(buf.samples), *hier, _ptr(d_h), _ptr(d_c),
+                                 _ptr(buf.dsamples), zb, zn, *extra, st), name)
     g_bias = torch.empty(buf.nb[0] + buf.nb[1], dtype=torch.float32, device=dev)
     main = torch.cuda.current_stream(dev)
     # (with more than one rank RCCL brings a fifth stream; the package asks the runtime for eight hardware queues then
@@ -867,7 +917,8 @@ def pinhole_rays(pose, pose_body, pix, H, W, focal, cx, cy):
     return torch.cat(parts, 1).contiguous()
 
 
-def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, signal_trainer=None, rays=None, bounds=None):
+def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, signal_trainer=None, rays=None, bounds=None,
+                 want_stats=False):
     """Differentiable (w.r.t. the decoder parameters and the two signals) two-field render of the
     pixels `pix_index` [n] (int32, y*W+x): coarse (frame.n_fine == 0, the reference's step) or hierarchical (64 / 128
     fine samples at detached depths; buf = TrainBuffers(..., n_fine=...)).  Returns rgb_head, rgb_com [n,3].  Fold and its backward run in HIP, the
@@ -878,7 +929,13 @@ def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z
     contiguous (o_head, d_head, o_torso, d_torso: engine.pack_rays; directions of any length), bg [n,3] = the background of ray r,
     bounds None or float32 [n,2] = (near, far) per ray; the frame's poses, intrinsics, H, W are ignored (FusedTrainRaysFn).  Anything
     else is a ValueError naming the argument, before any launch.  Rays that require grad (f32 tier; e.g. pinhole_rays of a learnable
-    pose) get their gradient from the backward; bounds and the fine depths stay constants."""
+    pose) get their gradient from the backward; bounds and the fine depths stay constants.
+    want_stats: returns rgb_head, rgb_com, stats with stats [n,4] = (acc_head, depth_head, acc_com, depth_com): per ray the opacity
+    sum_FG w and the expected depth sum_FG w z (premultiplied, units of near / far) of the head image and of the composite, FG = every
+    sample but the background plane (the definition of PackedDecoder's aux outputs).  Differentiable w.r.t. everything
+    the colours are - a mask, entropy or depth loss trains through it; both tiers (the stats code is f32 on the f32 samples)."""
+    if rays is None and pix_index is None and want_stats:
+        raise ValueError("render_train: want_stats needs pix_index or rays (the stats call takes the pixel ids as data)")
     if rays is not None or bounds is not None:
         if rays is None:
             raise ValueError("render_train: bounds are the per-ray (near, far) of caller-supplied rays: rays is None")
@@ -904,8 +961,10 @@ def render_train(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z
         if node is None or node is not sig_torso.grad_fn or type(node).__name__ != "_SignalFnBackward":
             signal_trainer = None
     if rays is not None:
-        return FusedTrainRaysFn.apply(sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, signal_trainer)
-    return FusedTrainFn.apply(sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, signal_trainer)
+        fn = FusedTrainRaysStatsFn if want_stats else FusedTrainRaysFn
+        return fn.apply(sig_head, sig_torso, buf, frame, bg, rays, bounds, z_shape, z_app, signal_trainer)
+    fn = FusedTrainStatsFn if want_stats else FusedTrainFn
+    return fn.apply(sig_head, sig_torso, buf, frame, bg, pix_index, z_shape, z_app, signal_trainer)
 
 
 def render_train_loss(dec, buf, frame, bg, pix_index, sig_head, sig_torso, z_shape, z_app, img_head, img_com,

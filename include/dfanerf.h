@@ -74,7 +74,8 @@ const char* dfn_last_error(void);
  * + dfn_train_rays_fwd, dfn_train_rays_fwd_hier, dfn_composite_bwd_rays_z, dfn_composite_bwd_hier_rays_z (the fused training step on
  * caller-supplied rays; f32 and bf16; nothing else changes, the version string stays); + dfn_composite_bwd_rays_zg,
  * dfn_composite_bwd_hier_rays_zg, dfn_points_grad, dfn_rays_grad (ray gradients of that step; f32; nothing else changes, the version
- * string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
+ * string stays); + dfn_composite_stats, dfn_composite_bwd_stats (per-ray opacity and expected depth of the training step and their
+ * gradient; both training tiers; nothing else changes, the version string stays).  DFN_WIDTH_128 (a flag in the tier argument of the inference entry
  * points; no new symbol).  0.3: + DFN_TIER_F16X3 in the inference entry points (dfn_packed_bytes,
  * dfn_pack_plan, dfn_pack_weights, dfn_bias_floats, dfn_fold_bias, dfn_render_fwd, dfn_render_fwd_u8, dfn_decoder_fwd).  0.2 (round 6): + dfn_wgrad_plan, dfn_get_rays_strided, dfn_weight_bias_grad_partials_part; DFN_FIELD_LISTENER accepted by the
  * training entry points; DfnFrame.n_coarse 32 / 64 / 128.  Since round 5 (still "0.1" then): dfn_weight_bias_grad_partials only fills
@@ -458,6 +459,33 @@ int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, con
                                    const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
                                    const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
                                    float* d_norm, void* stream);
+/* OPACITY and EXPECTED DEPTH of the training step, with gradients: what dfn_render_fwd_aux hands out for inference, on the samples the
+ * recording forward (dfn_train_fwd[_hier] / dfn_train_rays_fwd[_hier]) left on the device.  Per ray, over the step's final samples in
+ * depth order (the n_coarse coarse ones, or the merged n_coarse + n_fine) and FG = every sample but the last when concate_bg, all of
+ * them otherwise:
+ *   stats  f32 [ray_count, 4], out = acc_head, depth_head, acc_com, depth_com;  acc = sum_FG w_i, depth = sum_FG w_i * z_i (premultiplied,
+ *          in the units of near / far), w the weights of calc_volume_weights (MAIN:169-179) on the head field alone with |d_head|, or on
+ *          composite_function's summed density (MAIN:146-166) with |d_torso|; z_i in the forward's arithmetic.
+ * Exactly one of pix_index (int32 [ray_count]) / rays (f32 [ray_count, 12]) is given; bounds (f32 [ray_count, 2] or NULL) with rays
+ * only.  Hierarchical iff frame->n_fine > 0: then z_all and ranks (the forward's) are required.  fields == 2 only; counts: the
+ * backward's (32 / 64 / 128 coarse, or 64 + 64 | 128).  The background is not read.  Fixed summation order (a lane adds its positions
+ * in index order, then partners at XOR distance 32 ... 1), no atomics: bit-reproducible.  The weights are formed with the operations
+ * of the compositing backward, so dfn_composite_bwd_stats differentiates what this call wrote.  Depths and bounds are constants.
+ * DFN_E_ARG with the rule in the message, before any device work: a NULL pointer, both or neither ray source, bounds without rays,
+ * fields != 2, other counts, z_all / ranks missing.  An empty launch returns DFN_OK. */
+int dfn_composite_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* samples,
+                        const float* z_all, const uint8_t* ranks, float* stats, void* stream);
+/* ... and the compositing backward of a loss that reads them (MAIN:169-179 / 146-166 under autograd, with acc and depth as further
+ * outputs): the _z / _rays_z / _rays_zg family in one call - the ray source as above, z_all / ranks in the hierarchical step, zero_buf /
+ * zero_floats as in dfn_composite_bwd_z - plus
+ *   d_stats  f32 [ray_count, 4] = dL/d stats: adds [i in FG] * (g_acc + g_depth * z_i) to dL/dw_i of the image concerned, nothing else
+ *   d_norm   NULL, or with rays f32 [ray_count, 2], out: the gradient of the two ray norms (as dfn_composite_bwd_rays_zg), stats included
+ * d_rgb_com is required.  With d_stats == 0 every output equals the matching call of that family.  The refusals of dfn_composite_stats,
+ * plus: no background, an unaligned zero_buf, d_norm without rays. */
+int dfn_composite_bwd_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* bg_f32,
+                            const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
+                            const float* d_rgb_com, const float* d_stats, float* dsamples, float* zero_buf, long zero_floats, float* d_norm,
+                            void* stream);
 /* dL/d(point) and dL/d(unit view direction) of every evaluated point of one field, after dfn_mlp_bwd has written dy_T (on the stream
  * that owns it): differentiates the positional encodings (DEC:257-275) and the layers that read them (DEC:291-311, 321-325; the
  * deformation field DEC:109-134 with its residual DEC:299; the view layer DEC:337-340).
