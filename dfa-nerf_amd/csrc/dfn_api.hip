@@ -843,161 +843,9 @@ int dfn_mse_loss_u8(const float* rgb_head, const float* rgb_com, const uint8_t* 
                                     (hipStream_t)stream), "mse_loss_kernel");
 }
 
-struct BwdReq {
-    const char* who;            // the entry point; the _z forms of the pixel-id step report under the name without _z
-    bool hier, on_rays;         // on_rays: the step on caller-supplied rays (dfn_composite_bwd[_hier]_rays_z; no pixel ids)
-    const DfnFrame* frame;
-    const int32_t* pix_index;
-    const float *rays, *bounds, *bg_f32;
-    const uint8_t* bg_u8;
-    const float *samples, *z_all;
-    const uint8_t* ranks;
-    const float *d_rgb_head, *d_rgb_com;
-    float *dsamples, *zero_buf;
-    long zero_floats;
-    void* stream;
-};
-static int composite_bwd_impl(const BwdReq& q) {
-    const bool hier = q.hier, rin = q.on_rays;
-    const std::string who = q.who;
-    const DfnFrame* frame = q.frame;
-    if (rin && !q.rays)
-        return fail(DFN_E_ARG, who + ": rays is NULL (" + (hier ? "dfn_composite_bwd_hier_z" : "dfn_composite_bwd_z") +
-                                   " rebuilds the frame's own pinhole rays)");
-    if (rin && q.zero_buf && (((unsigned long)q.zero_buf & 15) || q.zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
-    if (rin && frame && frame->fields != 2)
-        return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
-    if (!frame || !q.samples || (hier && (!q.z_all || !q.ranks)) || !q.d_rgb_head || !q.dsamples || (!q.bg_f32 && !q.bg_u8))
-        return fail(DFN_E_ARG, who + ": bad argument");
-    if (hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
-        return fail(DFN_E_ARG, who + ": 64 coarse + 64 or 128 fine samples");
-    if (!hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
-        return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (dfn_composite_bwd_hier)");
-    if (frame->ray_count <= 0) return DFN_OK;
-    CompositeBwdRaysArgs A{};           // (the plain launches take its base: the block they have always had)
-    A.frame = *frame;
-    A.pix_index = q.pix_index;
-    A.bg_f32 = q.bg_f32;
-    A.bg_u8 = q.bg_u8;
-    A.samples = q.samples;
-    A.d_rgb_head = q.d_rgb_head;
-    A.d_rgb_com = q.d_rgb_com;
-    A.dsamples = q.dsamples;
-    A.z_all = q.z_all;            // (hierarchical step only)
-    A.ranks = q.ranks;
-    A.zero_buf = q.zero_buf;
-    A.zero_floats = q.zero_buf ? q.zero_floats : 0;
-    hipStream_t st = (hipStream_t)q.stream;
-    if (rin) {
-        A.rays = q.rays;
-        A.bounds = q.bounds;
-        return launched(launch_composite_bwd_rays(A, hier, st), hier ? "composite_bwd_hier_kernel(rays)" : "composite_bwd_kernel(rays)");
-    }
-    if (hier) return launched(launch_composite_bwd_hier(A, st), "composite_bwd_hier_kernel");
-    return launched(launch_composite_bwd(A, st), "composite_bwd_kernel");
-}
-int dfn_composite_bwd(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
-                      const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
-                      void* stream) {
-    return composite_bwd_impl({.who = "dfn_composite_bwd", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples,
-                               .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .stream = stream});
-}
-int dfn_composite_bwd_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
-                        const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
-                        float* zero_buf, long zero_floats, void* stream) {
-    if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0))
-        return fail(DFN_E_ARG, "dfn_composite_bwd_z: zero_buf must be 16-byte aligned");
-    return composite_bwd_impl({.who = "dfn_composite_bwd", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples,
-                               .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats,
-                               .stream = stream});
-}
-int dfn_composite_bwd_hier(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
-                           const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
-                           const float* d_rgb_com, float* dsamples, void* stream) {
-    return composite_bwd_impl({.who = "dfn_composite_bwd_hier", .hier = true, .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
-                               .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
-                               .stream = stream});
-}
-int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
-                             const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
-                             const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream) {
-    if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0))
-        return fail(DFN_E_ARG, "dfn_composite_bwd_hier_z: zero_buf must be 16-byte aligned");
-    return composite_bwd_impl({.who = "dfn_composite_bwd_hier", .hier = true, .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
-                               .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
-                               .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
-}
-
-int dfn_composite_bwd_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
-                             const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
-                             long zero_floats, void* stream) {
-    return composite_bwd_impl({.who = "dfn_composite_bwd_rays_z", .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds, .bg_f32 = bg_f32,
-                               .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf,
-                               .zero_floats = zero_floats, .stream = stream});
-}
-int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
-                                  const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
-                                  const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
-                                  void* stream) {
-    return composite_bwd_impl({.who = "dfn_composite_bwd_hier_rays_z", .hier = true, .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds,
-                               .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head,
-                               .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
-}
-
-// ---- ray gradients of the fused step (f32 tier) ---------------------------------------------------------------------------------
-// the _rays_z forms + d_norm: the shared checks (under the entry point's own name), then the <.., RAYS, DN> kernels
-static int composite_bwd_zg_impl(const BwdReq& q, float* d_norm) {
-    const std::string who = q.who;
-    if (!d_norm) return fail(DFN_E_ARG, who + ": d_norm is NULL (" + (q.hier ? "dfn_composite_bwd_hier_rays_z" : "dfn_composite_bwd_rays_z") +
-                                        " is the form without the norm gradients)");
-    const DfnFrame* frame = q.frame;
-    if (!q.rays) return fail(DFN_E_ARG, who + ": rays is NULL");
-    if (q.zero_buf && (((unsigned long)q.zero_buf & 15) || q.zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
-    if (frame && frame->fields != 2)
-        return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
-    if (!frame || !q.samples || (q.hier && (!q.z_all || !q.ranks)) || !q.d_rgb_head || !q.dsamples || (!q.bg_f32 && !q.bg_u8))
-        return fail(DFN_E_ARG, who + ": bad argument");
-    if (q.hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
-        return fail(DFN_E_ARG, who + ": 64 coarse + 64 or 128 fine samples");
-    if (!q.hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
-        return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (dfn_composite_bwd_hier_rays_zg)");
-    if (frame->ray_count <= 0) return DFN_OK;
-    CompositeBwdRaysGArgs A{};
-    A.frame = *frame;
-    A.bg_f32 = q.bg_f32;
-    A.bg_u8 = q.bg_u8;
-    A.samples = q.samples;
-    A.d_rgb_head = q.d_rgb_head;
-    A.d_rgb_com = q.d_rgb_com;
-    A.dsamples = q.dsamples;
-    A.z_all = q.z_all;
-    A.ranks = q.ranks;
-    A.zero_buf = q.zero_buf;
-    A.zero_floats = q.zero_buf ? q.zero_floats : 0;
-    A.rays = q.rays;
-    A.bounds = q.bounds;
-    A.d_norm = d_norm;
-    return launched(launch_composite_bwd_rays_g(A, q.hier, (hipStream_t)q.stream),
-                    q.hier ? "composite_bwd_hier_kernel(rays, d_norm)" : "composite_bwd_kernel(rays, d_norm)");
-}
-int dfn_composite_bwd_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
-                              const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
-                              long zero_floats, float* d_norm, void* stream) {
-    return composite_bwd_zg_impl({.who = "dfn_composite_bwd_rays_zg", .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds, .bg_f32 = bg_f32,
-                                  .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
-                                  .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream}, d_norm);
-}
-int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
-                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
-                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
-                                   float* d_norm, void* stream) {
-    return composite_bwd_zg_impl({.who = "dfn_composite_bwd_hier_rays_zg", .hier = true, .on_rays = true, .frame = frame, .rays = rays, .bounds = bounds,
-                                  .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head,
-                                  .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream},
-                                 d_norm);
-}
-// ---- opacity and expected depth of the training step, and the compositing backward of a loss that reads them -----------------------
-// the checks the two entry points share: the ray source, two fields, the backward's counts, the hierarchical extras
+// ---- the compositing backward of the fused step, its opacity / expected depth, and the backward of a loss that reads them -------
+// the checks of the two entry points that name their ray source by which pointer is given: the source, two fields, the counts, the
+// hierarchical extras
 static int stats_source_checks(const std::string& who, const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds,
                                const float* z_all, const uint8_t* ranks) {
     if (!pix_index == !rays)
@@ -1010,6 +858,156 @@ static int stats_source_checks(const std::string& who, const DfnFrame* frame, co
         return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, or 64 coarse + 64 or 128 fine samples");
     if (hier && (!z_all || !ranks)) return fail(DFN_E_ARG, who + ": the hierarchical step (n_fine > 0) needs z_all and ranks");
     return DFN_OK;
+}
+// one request of the compositing backward, whichever entry point it came through
+enum BwdForm { BY_PIXEL, ON_RAYS, ON_RAYS_G, WITH_STATS };      // pixel ids | caller-supplied rays | ... + d_norm | dfn_composite_bwd_stats
+struct BwdReq {
+    const char* who;            // the name refusals are reported under (the _z forms of the pixel-id step: the name without _z) ...
+    const char* who_z;          // ... but for a misaligned zero_buf, when this is given
+    BwdForm form;
+    bool hier;                  // (WITH_STATS: frame->n_fine > 0 instead)
+    const DfnFrame* frame;
+    const int32_t* pix_index;
+    const float *rays, *bounds, *bg_f32;
+    const uint8_t* bg_u8;
+    const float *samples, *z_all;
+    const uint8_t* ranks;
+    const float *d_rgb_head, *d_rgb_com, *d_stats;
+    float *dsamples, *zero_buf;
+    long zero_floats;
+    float* d_norm;
+    void* stream;
+};
+// Validates, then fills the one launch block; nothing touches the device before every check has passed, and an empty request
+// (ray_count <= 0) is DFN_OK after them.  Order of the refusals (the first that applies is reported), per form:
+//   BY_PIXEL     zero_buf alignment (under the _z name) > bad argument > hierarchical counts > coarse counts
+//   ON_RAYS      rays NULL > zero_buf alignment > fields > bad argument > hierarchical counts > coarse counts
+//   ON_RAYS_G    d_norm NULL > rays NULL > zero_buf alignment > fields > bad argument > hierarchical counts > coarse counts
+//   WITH_STATS   a NULL pointer > no background > ray source > bounds without rays > fields > counts > z_all / ranks > d_norm without
+//                rays > zero_buf alignment
+static int composite_bwd_request(const BwdReq& q) {
+    const std::string who = q.who;
+    const DfnFrame* frame = q.frame;
+    const bool R = q.form == ON_RAYS, G = q.form == ON_RAYS_G, S = q.form == WITH_STATS;
+    if (S) {
+        if (!frame || !q.samples || !q.d_rgb_head || !q.d_rgb_com || !q.d_stats || !q.dsamples)
+            return fail(DFN_E_ARG, who + ": a NULL pointer (frame, samples, d_rgb_head, d_rgb_com, d_stats, dsamples)");
+        if (!q.bg_f32 && !q.bg_u8) return fail(DFN_E_ARG, who + ": no background given");
+        if (stats_source_checks(who, frame, q.pix_index, q.rays, q.bounds, q.z_all, q.ranks) != DFN_OK) return DFN_E_ARG;
+        if (q.d_norm && !q.rays) return fail(DFN_E_ARG, who + ": d_norm is the gradient of the norms of caller-supplied rays (rays is NULL)");
+    }
+    const bool hier = S ? frame->n_fine > 0 : q.hier;
+    if (G && !q.d_norm)
+        return fail(DFN_E_ARG, who + ": d_norm is NULL (" + (hier ? "dfn_composite_bwd_hier_rays_z" : "dfn_composite_bwd_rays_z") +
+                                   " is the form without the norm gradients)");
+    if (R && !q.rays)
+        return fail(DFN_E_ARG, who + ": rays is NULL (" + (hier ? "dfn_composite_bwd_hier_z" : "dfn_composite_bwd_z") +
+                                   " rebuilds the frame's own pinhole rays)");
+    if (G && !q.rays) return fail(DFN_E_ARG, who + ": rays is NULL");
+    if (q.zero_buf && (((unsigned long)q.zero_buf & 15) || q.zero_floats < 0))
+        return fail(DFN_E_ARG, std::string(q.who_z ? q.who_z : q.who) + ": zero_buf must be 16-byte aligned");
+    if (!S) {
+        if ((R || G) && frame && frame->fields != 2)
+            return fail(DFN_E_ARG, who + ": the training step renders two fields (fields == 2; a rays row is o_head, d_head, o_torso, d_torso)");
+        if (!frame || !q.samples || (hier && (!q.z_all || !q.ranks)) || !q.d_rgb_head || !q.dsamples || (!q.bg_f32 && !q.bg_u8))
+            return fail(DFN_E_ARG, who + ": bad argument");
+        if (hier && (frame->n_coarse != 64 || (frame->n_fine != 64 && frame->n_fine != 128)))
+            return fail(DFN_E_ARG, who + ": 64 coarse + 64 or 128 fine samples");
+        if (!hier && (!coarse_ok(frame->n_coarse) || frame->n_fine != 0))
+            return fail(DFN_E_ARG, who + ": 32, 64 or 128 coarse samples, no fine ones (" +
+                                       (G ? "dfn_composite_bwd_hier_rays_zg" : "dfn_composite_bwd_hier") + ")");
+    }
+    if (frame->ray_count <= 0) return DFN_OK;
+    CompositeBwdArgs A{};
+    A.frame = *frame;
+    A.pix_index = q.pix_index;
+    A.bg_f32 = q.bg_f32;
+    A.bg_u8 = q.bg_u8;
+    A.samples = q.samples;
+    A.d_rgb_head = q.d_rgb_head;
+    A.d_rgb_com = q.d_rgb_com;
+    A.dsamples = q.dsamples;
+    A.z_all = q.z_all;            // (hierarchical step only)
+    A.ranks = q.ranks;
+    A.zero_buf = q.zero_buf;
+    A.zero_floats = q.zero_buf ? q.zero_floats : 0;
+    A.rays = q.rays;
+    A.bounds = q.bounds;
+    A.d_norm = q.d_norm;
+    A.d_stats = q.d_stats;
+    static const char* const of_form[] = {"", "(rays)", "(rays, d_norm)", "(stats)"};
+    const std::string kernel = std::string(hier ? "composite_bwd_hier_kernel" : "composite_bwd_kernel") + of_form[q.form];
+    return launched(launch_composite_bwd(A, (hipStream_t)q.stream), kernel.c_str());
+}
+int dfn_composite_bwd(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
+                      const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
+                      void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8,
+                                  .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .stream = stream});
+}
+int dfn_composite_bwd_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
+                        const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples,
+                        float* zero_buf, long zero_floats, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd", .who_z = "dfn_composite_bwd_z", .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32,
+                                  .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples,
+                                  .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
+}
+int dfn_composite_bwd_hier(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
+                           const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
+                           const float* d_rgb_com, float* dsamples, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_hier", .hier = true, .frame = frame, .pix_index = pix_index, .bg_f32 = bg_f32,
+                                  .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks, .d_rgb_head = d_rgb_head,
+                                  .d_rgb_com = d_rgb_com, .dsamples = dsamples, .stream = stream});
+}
+int dfn_composite_bwd_hier_z(const DfnFrame* frame, const int32_t* pix_index, const float* bg_f32, const uint8_t* bg_u8,
+                             const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
+                             const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_hier", .who_z = "dfn_composite_bwd_hier_z", .hier = true, .frame = frame,
+                                  .pix_index = pix_index, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks,
+                                  .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf,
+                                  .zero_floats = zero_floats, .stream = stream});
+}
+int dfn_composite_bwd_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                             const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                             long zero_floats, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_rays_z", .form = ON_RAYS, .frame = frame, .rays = rays, .bounds = bounds,
+                                  .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com,
+                                  .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .stream = stream});
+}
+int dfn_composite_bwd_hier_rays_z(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                  const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                  const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                  void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_hier_rays_z", .form = ON_RAYS, .hier = true, .frame = frame, .rays = rays,
+                                  .bounds = bounds, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks,
+                                  .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf,
+                                  .zero_floats = zero_floats, .stream = stream});
+}
+// ... + d_norm: the ray gradients of the fused step (f32 tier)
+int dfn_composite_bwd_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32, const uint8_t* bg_u8,
+                              const float* samples, const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf,
+                              long zero_floats, float* d_norm, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_rays_zg", .form = ON_RAYS_G, .frame = frame, .rays = rays, .bounds = bounds,
+                                  .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com,
+                                  .dsamples = dsamples, .zero_buf = zero_buf, .zero_floats = zero_floats, .d_norm = d_norm, .stream = stream});
+}
+int dfn_composite_bwd_hier_rays_zg(const DfnFrame* frame, const float* rays, const float* bounds, const float* bg_f32,
+                                   const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks,
+                                   const float* d_rgb_head, const float* d_rgb_com, float* dsamples, float* zero_buf, long zero_floats,
+                                   float* d_norm, void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_hier_rays_zg", .form = ON_RAYS_G, .hier = true, .frame = frame, .rays = rays,
+                                  .bounds = bounds, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks,
+                                  .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .dsamples = dsamples, .zero_buf = zero_buf,
+                                  .zero_floats = zero_floats, .d_norm = d_norm, .stream = stream});
+}
+int dfn_composite_bwd_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* bg_f32,
+                            const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
+                            const float* d_rgb_com, const float* d_stats, float* dsamples, float* zero_buf, long zero_floats, float* d_norm,
+                            void* stream) {
+    return composite_bwd_request({.who = "dfn_composite_bwd_stats", .form = WITH_STATS, .frame = frame, .pix_index = pix_index, .rays = rays,
+                                  .bounds = bounds, .bg_f32 = bg_f32, .bg_u8 = bg_u8, .samples = samples, .z_all = z_all, .ranks = ranks,
+                                  .d_rgb_head = d_rgb_head, .d_rgb_com = d_rgb_com, .d_stats = d_stats, .dsamples = dsamples,
+                                  .zero_buf = zero_buf, .zero_floats = zero_floats, .d_norm = d_norm, .stream = stream});
 }
 int dfn_composite_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* samples,
                         const float* z_all, const uint8_t* ranks, float* stats, void* stream) {
@@ -1028,39 +1026,7 @@ int dfn_composite_stats(const DfnFrame* frame, const int32_t* pix_index, const f
     A.stats = stats;
     return launched(launch_composite_stats(A, (hipStream_t)stream), "composite_stats_kernel");
 }
-int dfn_composite_bwd_stats(const DfnFrame* frame, const int32_t* pix_index, const float* rays, const float* bounds, const float* bg_f32,
-                            const uint8_t* bg_u8, const float* samples, const float* z_all, const uint8_t* ranks, const float* d_rgb_head,
-                            const float* d_rgb_com, const float* d_stats, float* dsamples, float* zero_buf, long zero_floats, float* d_norm,
-                            void* stream) {
-    const std::string who = "dfn_composite_bwd_stats";
-    if (!frame || !samples || !d_rgb_head || !d_rgb_com || !d_stats || !dsamples)
-        return fail(DFN_E_ARG, who + ": a NULL pointer (frame, samples, d_rgb_head, d_rgb_com, d_stats, dsamples)");
-    if (!bg_f32 && !bg_u8) return fail(DFN_E_ARG, who + ": no background given");
-    if (stats_source_checks(who, frame, pix_index, rays, bounds, z_all, ranks) != DFN_OK) return DFN_E_ARG;
-    if (d_norm && !rays) return fail(DFN_E_ARG, who + ": d_norm is the gradient of the norms of caller-supplied rays (rays is NULL)");
-    if (zero_buf && (((unsigned long)zero_buf & 15) || zero_floats < 0)) return fail(DFN_E_ARG, who + ": zero_buf must be 16-byte aligned");
-    if (frame->ray_count <= 0) return DFN_OK;
-    CompositeBwdStatsArgs A{};
-    A.frame = *frame;
-    A.pix_index = pix_index;
-    A.bg_f32 = bg_f32;
-    A.bg_u8 = bg_u8;
-    A.samples = samples;
-    A.d_rgb_head = d_rgb_head;
-    A.d_rgb_com = d_rgb_com;
-    A.dsamples = dsamples;
-    A.z_all = z_all;
-    A.ranks = ranks;
-    A.zero_buf = zero_buf;
-    A.zero_floats = zero_buf ? zero_floats : 0;
-    A.rays = rays;
-    A.bounds = bounds;
-    A.d_norm = d_norm;
-    A.d_stats = d_stats;
-    const bool hier = frame->n_fine > 0;
-    return launched(launch_composite_bwd_stats(A, hier, rays != nullptr, d_norm != nullptr, (hipStream_t)stream),
-                    hier ? "composite_bwd_hier_kernel(stats)" : "composite_bwd_kernel(stats)");
-}
+// ---- ray gradients of the fused step (f32 tier) ---------------------------------------------------------------------------------
 // the tier argument of the two ray-gradient entry points: f32 only
 static int ray_grad_tier(int tier, const char* who) {
     if (no_width(tier, who) != DFN_OK) return DFN_E_ARG;

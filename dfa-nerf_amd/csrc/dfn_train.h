@@ -17,48 +17,29 @@ struct MlpBwdArgs {
     long NP;
 };
 
+// composite_bwd_kernel: one block for every form.  Which pointers are given says which form is launched (launch_composite_bwd)
 struct CompositeBwdArgs {
     DfnFrame frame;
-    const int* pix_index;
+    const int* pix_index;       // pixel-id forms: [rays], or null = ray_begin + ray
     const float* bg_f32;
     const unsigned char* bg_u8;
-    const float* samples;       // [rays][S][8], S = 64 + n_fine, evaluation order
+    const float* samples;       // [rays][S][8], S = n_coarse + n_fine, evaluation order
     const float* d_rgb_head;    // [rays][3]
     const float* d_rgb_com;     // [rays][3] or null
     float* dsamples;            // out [rays][S][8]
-    // hierarchical step only (launch_composite_bwd_hier): what the forward left about the merge
+    // hierarchical step (n_fine > 0): what the forward left about the merge
     const float* z_all;         // [rays][S] merged, sorted depths
     const unsigned char* ranks; // [rays][S] merged rank of evaluated point i
-    // optional: a buffer this launch also fills with zeros (the step's gradient buffer: its own fill launch was 9 us + a gap
-    // between the compositing backward and the dX chain)
-    float* zero_buf;
-    long zero_floats;
+    float* zero_buf;            // optional: a buffer this launch also fills with zeros ...
+    long zero_floats;           // ... and its length
+    // the step on caller-supplied rays (pix_index is not read: bg row r is ray r's), what the forward read
+    const float* rays;          // [rays][12] = o_head, d_head, o_torso, d_torso (the ray norms come from the directions)
+    const float* bounds;        // [rays][2] = (near, far) or null = frame.z_near / z_far (the coarse step's depths)
+    float* d_norm;              // rays forms, optional: out [rays][2] = dL/d|d_head| (through the head image's dist = dz |d_head|), dL/d|d_torso|
+    const float* d_stats;       // optional: [rays][4] = dL/d(acc_head, depth_head, acc_com, depth_com) of a loss that reads the stats
 };
-// the step on caller-supplied rays (dfn_composite_bwd_rays_z / _hier_rays_z: the <.., RAYS> kernels) gains what the forward read: rays
-// f32 [rays][12] = o_head, d_head, o_torso, d_torso (the ray norms come from the directions), bounds f32 [rays][2] = (near, far) or null
-// = frame.z_near / z_far (the coarse-only kernel's depths).  No pixel id (pix_index is not read): bg row r is ray r's.  A block of its
-// own behind the plain one, so that the plain kernels' argument segment - and with it their ISA - stays what it was
-struct CompositeBwdRaysArgs : CompositeBwdArgs {
-    const float* rays;
-    const float* bounds;
-};
-
-// ... and the ray-gradient forms of those two (dfn_composite_bwd_rays_zg / _hier_rays_zg: the <.., RAYS, DN> kernels) also leave the
-// gradient of the two ray norms: d_norm f32 [rays][2] = dL/d|d_head| (through the head image's dist = dz |d_head|) and dL/d|d_torso|
-// (through the composite's).  Again a block of its own behind the rays block: the kernels without it keep their argument segment
-struct CompositeBwdRaysGArgs : CompositeBwdRaysArgs {
-    float* d_norm;
-};
-
-// Opacity and expected depth of the training step (dfn_composite_stats: composite_stats_kernel) and their gradient
-// (dfn_composite_bwd_stats: the <.., STATS> instantiations of the two backward kernels).  d_stats f32 [rays][4] = dL/d(acc_head,
-// depth_head, acc_com, depth_com) travels in a block of its own behind whichever block the form has: the instantiations without it
-// keep their argument segment, and with it their instruction stream
-template <class Base> struct WithDStats : Base {
-    const float* d_stats;
-};
-typedef WithDStats<CompositeBwdRaysGArgs> CompositeBwdStatsArgs;      // what the launcher takes; each form is launched on its own slice
-// composite_stats_kernel: one block for all four forms (pixel ids | rays + bounds, coarse | hierarchical).  The background is not read
+// composite_stats_kernel (opacity and expected depth of the training step; their gradient is d_stats above): one block for all four
+// forms (pixel ids | rays + bounds, coarse | hierarchical).  The background is not read
 struct CompositeStatsArgs {
     DfnFrame frame;
     const int* pix_index;       // pixel-id form: [rays]
@@ -98,13 +79,10 @@ struct RaysGradArgs {
 hipError_t launch_mlp_bwd(int tier, int field, const MlpBwdArgs& A, hipStream_t st);
 hipError_t launch_mlp_bwd_bf16(bool torso, const MlpBwdArgs& A, hipStream_t st);     // dfn_bwd_bf16.hip
 void bwd_program_info(int tier, int field, ProgramInfo* out);
+// the compositing family: 32 / 64 / 128 coarse samples and no fine ones, or 64 coarse + 64 / 128 fine ones; fields == 2 wherever rays or
+// stats are involved (launch_composite_stats: always).  Anything else: hipErrorInvalidValue
 hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st);
-hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st);      // n_fine in {64, 128}
-hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st);      // fields == 2; counts as the two above
-hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier, hipStream_t st);  // ... + d_norm
-hipError_t launch_composite_stats(const CompositeStatsArgs& A, hipStream_t st);                      // fields == 2; the backward's counts
-// the compositing backward of a loss that also reads the stats: on_rays / with_norm select the form (with_norm needs on_rays)
-hipError_t launch_composite_bwd_stats(const CompositeBwdStatsArgs& A, bool hier, bool on_rays, bool with_norm, hipStream_t st);
+hipError_t launch_composite_stats(const CompositeStatsArgs& A, hipStream_t st);
 hipError_t launch_points_grad(int field, const PointsGradArgs& A, hipStream_t st);                 // f32 tier; field 0 head, 1 torso, 2 listener
 hipError_t launch_rays_grad(const RaysGradArgs& A, hipStream_t st);
 // Split-K partials: C [ksplit][c_stride] and dbias [ksplit][n_bias], one writer per element and slice (no atomics);

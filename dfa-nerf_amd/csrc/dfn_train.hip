@@ -28,8 +28,12 @@ void bwd_program_info(int tier, int field, ProgramInfo* out) {
 }
 
 // ================================================================================================
-// compositing backward: one wave per ray, 64 coarse samples = 64 lanes
+// compositing backward, and the opacity / expected depth of the training step: one wave per ray, four rays per workgroup
 // ================================================================================================
+// Each piece is stated once, as a function on the K positions a lane owns, and serves every form: the coarse step (K = 1: 32 / 64 samples,
+// lanes beyond the ray's samples idle; K = 2: 128) and the hierarchical one (S = 64 K merged samples, K = 2: 64 + 64, K = 3: 64 + 128), on
+// pixel ids or on caller-supplied rays (RAYS), with the norm gradients (DN) and with a loss that reads the stats (STATS).  The unit is
+// built without contraction, so a result's bits follow the written order of the operations.
 __device__ __forceinline__ float wave_excl_prod(float v, int lane) {
     float inc = v;
 #pragma unroll
@@ -50,10 +54,14 @@ __device__ __forceinline__ float wave_suffix_sum_excl(float v, int lane) {      
     float exc = __shfl_down(inc, 1);
     return lane == 63 ? 0.f : exc;
 }
-// weights w_i = a_i T_i of run_nerf_com_trainExpLater.py:169-179 and dL/d(sigma_i) given q_i = c_i . G
-struct WB {
-    float w, ds;
-};
+// sum over the wave in a fixed order: partners at XOR distance 32, 16, 8, 4, 2, 1 (oracle: wave_sum64); every lane ends with the sum
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// optional: the launch also fills a buffer with zeros (the step's gradient buffer: its own fill launch was 9 us + a gap between the
+// compositing backward and the dX chain)
 __device__ __forceinline__ void composite_zero_fill(const CompositeBwdArgs& A) {
     if (!A.zero_buf) return;
     const long n4 = A.zero_floats >> 2, stride = (long)gridDim.x * blockDim.x;
@@ -61,32 +69,9 @@ __device__ __forceinline__ void composite_zero_fill(const CompositeBwdArgs& A) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (blockIdx.x == 0 && threadIdx.x < (A.zero_floats & 3)) A.zero_buf[(n4 << 2) + threadIdx.x] = 0.f;
 }
-// the argument block of the compositing backward kernels: the plain block, or the rays form's longer one (dfn_train.h)
-// (DN: the ray-gradient forms, which also write d_norm - always with RAYS)
-// (STATS: the forms that also take d_stats - the form's own block with d_stats behind it)
-template <bool RAYS, bool DN = false, bool STATS = false> struct CompositeArgsOf { typedef CompositeBwdArgs type; };
-template <> struct CompositeArgsOf<true, false, false> { typedef CompositeBwdRaysArgs type; };
-template <> struct CompositeArgsOf<true, true, false> { typedef CompositeBwdRaysGArgs type; };
-template <bool RAYS, bool DN> struct CompositeArgsOf<RAYS, DN, true> { typedef WithDStats<typename CompositeArgsOf<RAYS, DN, false>::type> type; };
-// sum over the wave in a fixed order: partners at XOR distance 32, 16, 8, 4, 2, 1 (oracle: wave_sum64); every lane ends with the sum
-__device__ __forceinline__ float wave_sum_xor(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-// DN kernels: dL/d|d| of one image = (1 / |d|) sum_s dL/d(s_s) (s_s + 1e-6), s = the effective density weights_bwd_n / image_bwd
-// differentiated (alpha_s = 1 - exp(-(s_s + 1e-6) dz_s |d|): the norm reaches the image through dist only).  A lane adds its own
-// positions in index order, wave_sum_xor adds the lanes; lane 0 writes
-template <int N>
-__device__ __forceinline__ float norm_grad(const float (&ds)[N], const float (&s)[N], const bool (&live)[N], float nrm) {
-    float p = 0.f;
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (live[k]) p += ds[k] * (fmaxf(s[k], 0.f) + 1e-6f);
-    return wave_sum_xor(p) / nrm;
-}
-// RAYS kernels (dfn_composite_bwd_rays_z / _hier_rays_z): the norms of the two directions of row `ray` of A.rays (o_head, d_head,
-// o_torso, d_torso), in the arithmetic of the forward's norm3 (dfn_render_kernels.h)
+
+// ---- ray norms: |d_head|, |d_torso| in the arithmetic of the forward (norm3, dfn_render_kernels.h)
+// RAYS: the two directions of row `ray` of rays = (o_head, d_head, o_torso, d_torso)
 __device__ __forceinline__ void ray_row_norms(const float* rays, long ray, float (&nrm)[2]) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -95,11 +80,26 @@ __device__ __forceinline__ void ray_row_norms(const float* rays, long ray, float
         nrm[b] = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
     }
 }
+// pixel ids: the frame's own pinhole rays through pixel `pix`, one per field's pose
+__device__ __forceinline__ void pinhole_norms(const DfnFrame& F, int pix, float (&nrm)[2]) {
+    const int y = pix / F.W, x = pix - y * F.W;
+    const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const float* P = b ? F.pose_body : F.pose;
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])), __fmul_rn(-1.0f, P[4 * k + 2]));
+            acc = __fadd_rn(acc, __fmul_rn(d, d));
+        }
+        nrm[b] = sqrtf(acc);
+    }
+}
+
+// ---- a ray's samples as a lane sees them
 // the coarse depths in the forward's arithmetic (MAIN:617-618; torch.linspace(0, 1, NC): lower half step * i, upper half 1 - step *
-// (NC - 1 - i) as one fma), for rays_grad_kernel.  composite_bwd_kernel keeps the lambdas it has always had (tval / zval, the same
-// operations): written through these helpers the plain <1, false> instantiation came out with a different instruction stream, and
-// the existing kernels' ISA is held fixed.  tests/test_gpu_ray_grad.py holds the two statements together bit for bit
-// (test_rays_grad_depths_are_the_forwards).
+// (NC - 1 - i) as one fma)
 __device__ __forceinline__ float coarse_step(int NC) { return __fdiv_rn(1.0f, (float)(NC - 1)); }
 __device__ __forceinline__ float coarse_t(float step, int NC, int i) {
     return (i < NC / 2) ? __fmul_rn(step, (float)i) : fmaf(-step, (float)(NC - 1 - i), 1.0f);
@@ -107,626 +107,349 @@ __device__ __forceinline__ float coarse_t(float step, int NC, int i) {
 __device__ __forceinline__ float coarse_depth(float z_near, float z_far, float t) {
     return __fadd_rn(__fmul_rn(z_near, __fsub_rn(1.0f, t)), __fmul_rn(z_far, t));
 }
-// KL consecutive samples per lane (KL = 1: --N_samples 32 / 64, lanes beyond the ray's samples idle; KL = 2: 128), round 6.
-// Sample i = lane KL + k.  The scans run over the lanes' local products / sums and are carried across a lane's KL positions;
-// with KL = 1 and 64 samples the arithmetic is the round 1-5 kernel's.
-template <int KL>
-__device__ __forceinline__ void weights_bwd_n(const float (&sigma)[KL], const float (&dist)[KL], const float (&q)[KL],
-                                              const bool (&live)[KL], int lane, WB (&out)[KL]) {
-    float e[KL], a[KL], v[KL], T[KL], wq[KL];
-    float lp = 1.0f;
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-        e[k] = expf(-((fmaxf(sigma[k], 0.f) + 1e-6f) * dist[k]));
-        a[k] = live[k] ? 1.0f - e[k] : 0.f;
-        v[k] = live[k] ? 1.0f - a[k] + 1e-10f : 1.0f;
-        lp *= v[k];
-    }
-    float Tb = wave_excl_prod(KL == 1 ? v[0] : lp, lane);
-    float ls = 0.f;
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-        T[k] = Tb;
-        Tb *= v[k];
-        out[k].w = a[k] * T[k];
-        wq[k] = out[k].w * q[k];
-        ls += wq[k];
-    }
-    float suf = wave_suffix_sum_excl(KL == 1 ? wq[0] : ls, lane);      // over the lanes behind this one
-#pragma unroll
-    for (int k = KL - 1; k >= 0; --k) {
-        const float da = T[k] * q[k] - suf / v[k];
-        out[k].ds = da * dist[k] * e[k];             // d a / d sigma = dist * exp(-(sigma + 1e-6) dist)
-        suf += wq[k];
-    }
-}
-// RAYS: the step on caller-supplied rays - the norms from the directions of row `ray`, the depths between that ray's (near, far) when
-// bounds are given, the background of the last sample from row `ray`; everything behind the geometry is the same code
-// DN (with RAYS): also d_norm[ray] = (dL/d|d_head|, dL/d|d_torso|), the ray-gradient step's input (dfn_composite_bwd_rays_zg)
-// STATS (dfn_composite_bwd_stats): the loss also reads stats = (acc_head, depth_head, acc_com, depth_com) of composite_stats_kernel,
-// acc = sum_FG w_i, depth = sum_FG w_i z_i.  q[i] IS dL/dw_i, so the stats add [i in FG] (g_acc + g_depth z_i) to q of their image and
-// nothing else: d sigma, the blend's branches, the ReLU masks and d_norm (norm_grad reads ds) follow through the code below
-template <int KL, bool RAYS = false, bool DN = false, bool STATS = false>
-__global__ void composite_bwd_kernel(const typename CompositeArgsOf<RAYS, DN, STATS>::type A) {
-    static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
-    composite_zero_fill(A);
-    const int lane = threadIdx.x & 63;
-    const long ray = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ray >= A.frame.ray_count) return;
-    const DfnFrame& F = A.frame;
-    const int NC = F.n_coarse;
-    // (RAYS: the background row of a supplied ray is the ray's own)
-    const int pix = RAYS ? (int)ray : A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
-    float nrm[2];
-    float nf[2] = {0.f, 0.f};                        // RAYS: this ray's (near, far)
-    if constexpr (RAYS) {
-        ray_row_norms(A.rays, ray, nrm);
-        nf[0] = A.bounds ? A.bounds[ray * 2] : F.z_near;             // (uniform over the launch)
-        nf[1] = A.bounds ? A.bounds[ray * 2 + 1] : F.z_far;
-    } else {
-        // geometry (same arithmetic as the forward)
-        const int y = pix / F.W, x = pix - y * F.W;
-        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float* P = b ? F.pose_body : F.pose;
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
-                                          __fmul_rn(-1.0f, P[4 * k + 2]));
-                acc = __fadd_rn(acc, __fmul_rn(d, d));
-            }
-            nrm[b] = sqrtf(acc);
-        }
-    }
-    const float step = __fdiv_rn(1.0f, (float)(NC - 1));
-    auto tval = [&](int i) { return (i < NC / 2) ? __fmul_rn(step, (float)i) : fmaf(-step, (float)(NC - 1 - i), 1.0f); };
-    auto zval = [&](int i) {
-        const float t = tval(i);
-        if constexpr (RAYS) return __fadd_rn(__fmul_rn(nf[0], __fsub_rn(1.0f, t)), __fmul_rn(nf[1], t));
-        else return __fadd_rn(__fmul_rn(F.z_near, __fsub_rn(1.0f, t)), __fmul_rn(F.z_far, t));
-    };
-    const bool cbg = F.concate_bg != 0;
-    bool live[KL], last[KL], h_is_bg[KL];
-    float dz[KL], sg_h[KL], sg_t_raw[KL], ch[KL][3], ct[KL][3], sh[KL];
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-        const int i = lane * KL + k;
-        live[k] = i < NC;
-        const int ii = live[k] ? i : NC - 1;
-        last[k] = ii == NC - 1;
-        dz[k] = last[k] ? F.last_dist : __fsub_rn(zval(ii + 1), zval(ii));
-        const float* sm = A.samples + (ray * NC + ii) * 8;
-        sg_h[k] = sm[0];
-        sg_t_raw[k] = sm[4];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            ch[k][c] = sm[1 + c];
-            ct[k][c] = sm[5 + c];
-        }
-        h_is_bg[k] = cbg && last[k];
-        if (h_is_bg[k]) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                ch[k][c] = A.bg_u8 ? __fdiv_rn((float)A.bg_u8[(size_t)pix * 3 + c], 255.0f) : A.bg_f32[(size_t)pix * 3 + c];
-        }
-        sh[k] = fmaxf(sg_h[k], 0.f);
-    }
-    float Gh[3], Gc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        Gh[k] = A.d_rgb_head[ray * 3 + k];
-        Gc[k] = A.d_rgb_com ? A.d_rgb_com[ray * 3 + k] : 0.f;
-    }
-    float gs[4] = {0.f, 0.f, 0.f, 0.f}, qs[2][KL];       // STATS: dL/d stats of this ray, and the term of each image's q
-    if constexpr (STATS) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gs[j] = A.d_stats[ray * 4 + j];
-#pragma unroll
-        for (int k = 0; k < KL; ++k) {
-            const bool fg = live[k] && !(cbg && last[k]);
-            const float z = zval(live[k] ? lane * KL + k : NC - 1);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) qs[b][k] = fg ? gs[2 * b] + gs[2 * b + 1] * z : 0.f;
-        }
-    }
-    float d_sg_h[KL], d_ch[KL][3], d_sg_t[KL], d_ct[KL][3];
-    // ---- head-only image: s = relu(sg_h) (+1e-6 at the last sample), colour ch
-    {
-        float s1[KL], dist[KL], q[KL];
-        WB r[KL];
-#pragma unroll
-        for (int k = 0; k < KL; ++k) {
-            s1[k] = h_is_bg[k] ? sh[k] + 1e-6f : sh[k];
-            dist[k] = dz[k] * nrm[0];
-            q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
-            if constexpr (STATS) q[k] += qs[0][k];
-        }
-        weights_bwd_n<KL>(s1, dist, q, live, lane, r);
-        if constexpr (DN) {
-            float dsv[KL];
-#pragma unroll
-            for (int k = 0; k < KL; ++k) dsv[k] = r[k].ds;
-            const float g = norm_grad<KL>(dsv, s1, live, nrm[0]);
-            if (lane == 0) A.d_norm[ray * 2] = g;
-        }
-#pragma unroll
-        for (int k = 0; k < KL; ++k) {
-            d_sg_h[k] = (sg_h[k] > 0.f) ? r[k].ds : 0.f;
-            d_sg_t[k] = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                d_ch[k][c] = h_is_bg[k] ? 0.f : r[k].w * Gh[c];
-                d_ct[k][c] = 0.f;
-            }
-        }
-    }
-    // ---- composite image (run_nerf_com_trainExpLater.py:146-166)
-    if (A.frame.fields == 2) {
-        float ssum[KL], dist[KL], q[KL], sg_t[KL], st[KL], den[KL], wh[KL], wt[KL];
-        bool zero[KL];
-        WB r[KL];
-#pragma unroll
-        for (int k = 0; k < KL; ++k) {
-            sg_t[k] = (cbg && last[k]) ? 0.f : sg_t_raw[k];
-            st[k] = fmaxf(sg_t[k], 0.f);
-            if (cbg && last[k]) st[k] += 1e-6f;
-            ssum[k] = sh[k] + st[k];
-            zero[k] = ssum[k] == 0.f;
-            den[k] = zero[k] ? 1e-4f : ssum[k];
-            wh[k] = sh[k] / den[k];
-            wt[k] = st[k] / den[k];
-            float cm[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cm[c] = ch[k][c] * wh[k] + ct[k][c] * wt[k];
-            q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
-            if constexpr (STATS) q[k] += qs[1][k];
-            dist[k] = dz[k] * nrm[1];
-        }
-        weights_bwd_n<KL>(ssum, dist, q, live, lane, r);
-        if constexpr (DN) {
-            float dsv[KL];
-#pragma unroll
-            for (int k = 0; k < KL; ++k) dsv[k] = r[k].ds;
-            const float g = norm_grad<KL>(dsv, ssum, live, nrm[1]);
-            if (lane == 0) A.d_norm[ray * 2 + 1] = g;
-        }
-#pragma unroll
-        for (int k = 0; k < KL; ++k) {
-            const float gch = ch[k][0] * Gc[0] + ch[k][1] * Gc[1] + ch[k][2] * Gc[2];
-            const float gct = ct[k][0] * Gc[0] + ct[k][1] * Gc[1] + ct[k][2] * Gc[2];
-            const float dwh = r[k].w * gch, dwt = r[k].w * gct;
-            // wh = sh/den, wt = st/den, den = sh + st (or the constant 1e-4)
-            float dsh = r[k].ds + dwh / den[k], dst = r[k].ds + dwt / den[k];
-            if (!zero[k]) {
-                const float common = (dwh * sh[k] + dwt * st[k]) / (den[k] * den[k]);
-                dsh -= common;
-                dst -= common;
-            }
-            if (sg_h[k] > 0.f) d_sg_h[k] += dsh;
-            if (sg_t[k] > 0.f && !(cbg && last[k])) d_sg_t[k] += dst;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (!h_is_bg[k]) d_ch[k][c] += r[k].w * Gc[c] * wh[k];
-                d_ct[k][c] += r[k].w * Gc[c] * wt[k];
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KL; ++k) {
-        if (!live[k]) continue;
-        float* out = A.dsamples + (ray * NC + lane * KL + k) * 8;
-        out[0] = d_sg_h[k];
-        out[4] = d_sg_t[k];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            out[1 + c] = d_ch[k][c];
-            out[5 + c] = d_ct[k][c];
-        }
-    }
-}
-hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st) {
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    if (A.frame.n_coarse == 128) hipLaunchKernelGGL(composite_bwd_kernel<2>, dim3(blocks), dim3(256), 0, st, A);
-    else if (A.frame.n_coarse == 64 || A.frame.n_coarse == 32) hipLaunchKernelGGL(composite_bwd_kernel<1>, dim3(blocks), dim3(256), 0, st, A);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// ================================================================================================
-// compositing backward over the MERGED samples of the hierarchical training step (SURVEY.md 8(a) row H under autograd)
-// ================================================================================================
-// One wave per ray, S = 64 K merged samples (K = 2: 64 + 64, K = 3: 64 + 128): lane l owns the K consecutive merged
-// positions l K .. l K + K - 1.  The forward left every evaluated point's raw outputs in EVALUATION order (coarse points,
-// then the fine ones: the order of the recorded activations, which is what the dX chain walks), its merged rank, and the
-// merged depths; the fine depths are constants (no gradient through sample_pdf), so this is the same differentiation as
-// composite_bwd_kernel with run-time depths and the scans carried across a lane's K positions.
-// RAYS: as in composite_bwd_kernel - the norms and the background row only (the depths are z_all's)
-// STATS: as in composite_bwd_kernel, with z_i = z_all
-template <int K, bool RAYS = false, bool DN = false, bool STATS = false>
-__global__ __launch_bounds__(256) void composite_bwd_hier_kernel(const typename CompositeArgsOf<RAYS, DN, STATS>::type A) {
-    static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
-    constexpr int S = 64 * K;
-    __shared__ unsigned char inv_s[4][S];
-    composite_zero_fill(A);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long ray = (long)blockIdx.x * 4 + wv;
-    if (ray >= A.frame.ray_count) return;
-    const DfnFrame& F = A.frame;
-    const int pix = RAYS ? (int)ray : A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
-    float nrm[2];
-    if constexpr (RAYS) {
-        ray_row_norms(A.rays, ray, nrm);
-    } else {
-        const int y = pix / F.W, x = pix - y * F.W;
-        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float* P = b ? F.pose_body : F.pose;
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
-                                          __fmul_rn(-1.0f, P[4 * k + 2]));
-                acc = __fadd_rn(acc, __fmul_rn(d, d));
-            }
-            nrm[b] = sqrtf(acc);
-        }
-    }
-    // inverse of the rank map: merged position -> evaluation index
+// hierarchical step: the forward left each evaluated point's merged rank; this is the inverse, merged position -> evaluation index,
+// of one ray (one wave), in LDS (256 K bytes per workgroup)
+template <int K>
+__device__ __forceinline__ const unsigned char* invert_ranks(const unsigned char* ranks, int lane, int wv) {
+    __shared__ unsigned char inv_s[4][64 * K];
     unsigned char* inv = inv_s[wv];
 #pragma unroll
-    for (int m = 0; m < K; ++m) inv[A.ranks[ray * S + lane + 64 * m]] = (unsigned char)(lane + 64 * m);
+    for (int m = 0; m < K; ++m) inv[ranks[lane + 64 * m]] = (unsigned char)(lane + 64 * m);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool cbg = F.concate_bg != 0, two = F.fields == 2;
-    float Gh[3], Gc[3], bgc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        Gh[k] = A.d_rgb_head[ray * 3 + k];
-        Gc[k] = A.d_rgb_com ? A.d_rgb_com[ray * 3 + k] : 0.f;
-        bgc[k] = A.bg_u8 ? __fdiv_rn((float)A.bg_u8[(size_t)pix * 3 + k], 255.0f) : A.bg_f32[(size_t)pix * 3 + k];
-    }
-    // per owned position: everything the two images' backward needs
-    int ev[K];
-    float dz[K], sg_h[K], sg_t[K], ch[K][3], ct[K][3];
-    bool lastp[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int i = lane * K + k;
-        ev[k] = inv[i];
-        lastp[k] = i == S - 1;
-        const float z = A.z_all[ray * S + i];
-        dz[k] = lastp[k] ? F.last_dist : __fsub_rn(A.z_all[ray * S + i + 1], z);
-        const float4* sm = (const float4*)(A.samples + ((size_t)ray * S + ev[k]) * 8);
-        const float4 q0 = sm[0], q1 = sm[1];
-        sg_h[k] = q0.x; ch[k][0] = q0.y; ch[k][1] = q0.z; ch[k][2] = q0.w;
-        sg_t[k] = q1.x; ct[k][0] = q1.y; ct[k][1] = q1.z; ct[k][2] = q1.w;
-        if (cbg && lastp[k]) { ch[k][0] = bgc[0]; ch[k][1] = bgc[1]; ch[k][2] = bgc[2]; }
-    }
-    float qs[2][K];                // STATS: the stats' term of each image's q = dL/dw
-    if constexpr (STATS) {
-        float gs[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gs[j] = A.d_stats[ray * 4 + j];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float z = A.z_all[ray * S + lane * K + k];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) qs[b][k] = (cbg && lastp[k]) ? 0.f : gs[2 * b] + gs[2 * b + 1] * z;
-        }
-    }
-    // weights + d/d(sigma) of one image over the merged samples: s (effective sigma), dist, q = colour . G per position
-    auto image_bwd = [&](const float (&s)[K], const float (&dist)[K], const float (&q)[K], float (&w)[K], float (&ds)[K]) {
-        float e[K], a[K], v[K], pre[K];
-        float prod = 1.0f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            e[k] = expf(-((fmaxf(s[k], 0.f) + 1e-6f) * dist[k]));
-            a[k] = 1.0f - e[k];
-            v[k] = 1.0f - a[k] + 1e-10f;
-            pre[k] = prod;                       // product of this lane's earlier positions
-            prod *= v[k];
-        }
-        const float T0 = wave_excl_prod(prod, lane);          // transmittance in front of this lane's first position
-        float wq_sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            w[k] = a[k] * (T0 * pre[k]);
-            wq_sum += w[k] * q[k];
-        }
-        const float suf0 = wave_suffix_sum_excl(wq_sum, lane);     // sum of w q over the later lanes
-        float later = 0.f;                                         // ... plus this lane's later positions
-#pragma unroll
-        for (int k = K - 1; k >= 0; --k) {
-            const float da = (T0 * pre[k]) * q[k] - (suf0 + later) / v[k];
-            ds[k] = da * dist[k] * e[k];
-            later += w[k] * q[k];
-        }
-    };
-    bool all_live[K];              // (DN: every merged position holds a sample)
-#pragma unroll
-    for (int k = 0; k < K; ++k) all_live[k] = true;
-    float d_sg_h[K], d_sg_t[K], d_ch[K][3], d_ct[K][3];
-    {   // head-only image
-        float s1[K], dist[K], q[K], w[K], ds[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float sh = fmaxf(sg_h[k], 0.f);
-            s1[k] = (cbg && lastp[k]) ? sh + 1e-6f : sh;
-            dist[k] = dz[k] * nrm[0];
-            q[k] = ch[k][0] * Gh[0] + ch[k][1] * Gh[1] + ch[k][2] * Gh[2];
-            if constexpr (STATS) q[k] += qs[0][k];
-        }
-        image_bwd(s1, dist, q, w, ds);
-        if constexpr (DN) {
-            const float g = norm_grad<K>(ds, s1, all_live, nrm[0]);
-            if (lane == 0) A.d_norm[ray * 2] = g;
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const bool h_is_bg = cbg && lastp[k];
-            d_sg_h[k] = sg_h[k] > 0.f ? ds[k] : 0.f;
-            d_sg_t[k] = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                d_ch[k][c] = h_is_bg ? 0.f : w[k] * Gh[c];
-                d_ct[k][c] = 0.f;
-            }
-        }
-    }
-    if (two) {   // composite image (run_nerf_com_trainExpLater.py:146-166)
-        float ss[K], dist[K], q[K], w[K], ds[K], sh[K], stt[K], den[K], wh[K], wt[K];
-        bool zero[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float sgt = (cbg && lastp[k]) ? 0.f : sg_t[k];
-            sh[k] = fmaxf(sg_h[k], 0.f);
-            stt[k] = fmaxf(sgt, 0.f);
-            if (cbg && lastp[k]) stt[k] += 1e-6f;
-            ss[k] = sh[k] + stt[k];
-            zero[k] = ss[k] == 0.f;
-            den[k] = zero[k] ? 1e-4f : ss[k];
-            wh[k] = sh[k] / den[k];
-            wt[k] = stt[k] / den[k];
-            dist[k] = dz[k] * nrm[1];
-            float cm[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cm[c] = ch[k][c] * wh[k] + ct[k][c] * wt[k];
-            q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
-            if constexpr (STATS) q[k] += qs[1][k];
-        }
-        image_bwd(ss, dist, q, w, ds);
-        if constexpr (DN) {
-            const float g = norm_grad<K>(ds, ss, all_live, nrm[1]);
-            if (lane == 0) A.d_norm[ray * 2 + 1] = g;
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const bool h_is_bg = cbg && lastp[k];
-            const float gch = ch[k][0] * Gc[0] + ch[k][1] * Gc[1] + ch[k][2] * Gc[2];
-            const float gct = ct[k][0] * Gc[0] + ct[k][1] * Gc[1] + ct[k][2] * Gc[2];
-            const float dwh = w[k] * gch, dwt = w[k] * gct;
-            float dsh = ds[k] + dwh / den[k], dst = ds[k] + dwt / den[k];
-            if (!zero[k]) {
-                const float common = (dwh * sh[k] + dwt * stt[k]) / (den[k] * den[k]);
-                dsh -= common;
-                dst -= common;
-            }
-            if (sg_h[k] > 0.f) d_sg_h[k] += dsh;
-            if (sg_t[k] > 0.f && !(cbg && lastp[k])) d_sg_t[k] += dst;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (!h_is_bg) d_ch[k][c] += w[k] * Gc[c] * wh[k];
-                d_ct[k][c] += w[k] * Gc[c] * wt[k];
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float4* out = (float4*)(A.dsamples + ((size_t)ray * S + ev[k]) * 8);
-        out[0] = make_float4(d_sg_h[k], d_ch[k][0], d_ch[k][1], d_ch[k][2]);
-        out[1] = make_float4(d_sg_t[k], d_ct[k][0], d_ct[k][1], d_ct[k][2]);
-    }
+    return inv;
 }
-hipError_t launch_composite_bwd_hier(const CompositeBwdArgs& A, hipStream_t st) {
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    const int K = (64 + A.frame.n_fine) / 64;
-    if (K == 2) hipLaunchKernelGGL(composite_bwd_hier_kernel<2>, dim3(blocks), dim3(256), 0, st, A);
-    else if (K == 3) hipLaunchKernelGGL(composite_bwd_hier_kernel<3>, dim3(blocks), dim3(256), 0, st, A);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-// the two launches above on caller-supplied rays (a rays row holds both fields' rays: two fields only)
-hipError_t launch_composite_bwd_rays(const CompositeBwdRaysArgs& A, bool hier, hipStream_t st) {
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
-    if (!A.rays || A.frame.fields != 2) return hipErrorInvalidValue;
-    if (hier) {
-        if (nc != 64 || (A.frame.n_fine != 64 && A.frame.n_fine != 128)) return hipErrorInvalidValue;
-        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, true>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, true>), dim3(blocks), dim3(256), 0, st, A);
+// Lane l owns the K consecutive positions l K .. l K + K - 1 of the ray's n samples in depth order.  Per position: live (a sample is
+// there; an idle position stands on the last sample), last, the depth z, the distance dz to the next sample (last_dist behind the last)
+// and ev, the sample's row in the evaluation order of samples / dsamples.
+// Coarse: the depths of the linspace between the frame's (near, far) or, with RAYS, this ray's bounds; ev is the position.
+// Hierarchical: n = 64 K, the depths are z_all's (constants: no gradient through sample_pdf), ev goes through the inverted rank map.
+template <int K> struct LaneSamples {
+    int n, ev[K];
+    bool live[K], last[K];
+    float z[K], dz[K];
+};
+template <int K, bool HIER, bool RAYS, class Args>
+__device__ __forceinline__ void lane_samples(const Args& A, long ray, int lane, int wv, LaneSamples<K>& P) {
+    const DfnFrame& F = A.frame;
+    if constexpr (HIER) {
+        constexpr int S = 64 * K;
+        P.n = S;
+        const unsigned char* inv = invert_ranks<K>(A.ranks + ray * S, lane, wv);
+        const float* zr = A.z_all + ray * S;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int i = lane * K + k;
+            P.live[k] = true;
+            P.last[k] = i == S - 1;
+            P.ev[k] = inv[i];
+            P.z[k] = zr[i];
+            P.dz[k] = P.last[k] ? F.last_dist : __fsub_rn(zr[i + 1], P.z[k]);
+        }
     } else {
-        if ((nc != 128 && nc != 64 && nc != 32) || A.frame.n_fine != 0) return hipErrorInvalidValue;
-        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, true>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_bwd_kernel<1, true>), dim3(blocks), dim3(256), 0, st, A);
+        const int NC = F.n_coarse;
+        P.n = NC;
+        const float near = RAYS && A.bounds ? A.bounds[ray * 2] : F.z_near, far = RAYS && A.bounds ? A.bounds[ray * 2 + 1] : F.z_far;
+        const float step = coarse_step(NC);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int i = lane * K + k;
+            P.live[k] = i < NC;
+            P.ev[k] = P.live[k] ? i : NC - 1;
+            P.last[k] = P.ev[k] == NC - 1;
+            P.z[k] = coarse_depth(near, far, coarse_t(step, NC, P.ev[k]));
+            P.dz[k] = P.last[k] ? F.last_dist : __fsub_rn(coarse_depth(near, far, coarse_t(step, NC, P.ev[k] + 1)), P.z[k]);
+        }
     }
-    return hipGetLastError();
 }
-// ... and with the norm gradients (dfn_composite_bwd_rays_zg / _hier_rays_zg): instantiations of their own next to the ones above
-hipError_t launch_composite_bwd_rays_g(const CompositeBwdRaysGArgs& A, bool hier, hipStream_t st) {
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
-    if (!A.rays || !A.d_norm || A.frame.fields != 2) return hipErrorInvalidValue;
-    if (hier) {
-        if (nc != 64 || (A.frame.n_fine != 64 && A.frame.n_fine != 128)) return hipErrorInvalidValue;
-        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, true, true>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, true, true>), dim3(blocks), dim3(256), 0, st, A);
-    } else {
-        if ((nc != 128 && nc != 64 && nc != 32) || A.frame.n_fine != 0) return hipErrorInvalidValue;
-        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, true, true>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_bwd_kernel<1, true, true>), dim3(blocks), dim3(256), 0, st, A);
-    }
-    return hipGetLastError();
-}
-// ... and with d_stats (dfn_composite_bwd_stats): the <.., STATS> instantiation of the form, launched on the form's own block + d_stats
-template <class Base>
-static WithDStats<Base> stats_block(const CompositeBwdStatsArgs& A) {
-    WithDStats<Base> B{};
-    static_cast<Base&>(B) = static_cast<const Base&>(A);
-    B.d_stats = A.d_stats;
-    return B;
-}
-template <bool RAYS, bool DN>
-static hipError_t launch_composite_bwd_stats_t(const CompositeBwdStatsArgs& A, bool hier, hipStream_t st) {
-    const auto B = stats_block<typename CompositeArgsOf<RAYS, DN, false>::type>(A);
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
-    if (hier) {
-        if (K == 2) hipLaunchKernelGGL((composite_bwd_hier_kernel<2, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
-        else hipLaunchKernelGGL((composite_bwd_hier_kernel<3, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
-    } else {
-        if (nc == 128) hipLaunchKernelGGL((composite_bwd_kernel<2, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
-        else hipLaunchKernelGGL((composite_bwd_kernel<1, RAYS, DN, true>), dim3(blocks), dim3(256), 0, st, B);
-    }
-    return hipGetLastError();
-}
-static bool stats_counts_ok(const DfnFrame& F, bool hier) {
-    if (hier) return F.n_coarse == 64 && (F.n_fine == 64 || F.n_fine == 128);
-    return (F.n_coarse == 128 || F.n_coarse == 64 || F.n_coarse == 32) && F.n_fine == 0;
-}
-hipError_t launch_composite_bwd_stats(const CompositeBwdStatsArgs& A, bool hier, bool on_rays, bool with_norm, hipStream_t st) {
-    if (!A.d_stats || A.frame.fields != 2 || !stats_counts_ok(A.frame, hier) || (on_rays && !A.rays) || (with_norm && (!on_rays || !A.d_norm)))
-        return hipErrorInvalidValue;
-    if (with_norm) return launch_composite_bwd_stats_t<true, true>(A, hier, st);
-    if (on_rays) return launch_composite_bwd_stats_t<true, false>(A, hier, st);
-    return launch_composite_bwd_stats_t<false, false>(A, hier, st);
+// the densities the two images composite at one sample (run_nerf_com_trainExpLater.py:146-166, 706-709): sh, st = the fields' ReLU'd
+// sigmas (bgp = the background stands at this sample: no torso density, and 1e-6 on each image), s1 = the head image's, ss = the composite's
+struct Sigmas {
+    float sh, st, s1, ss;
+};
+__device__ __forceinline__ Sigmas effective_sigmas(float sg_h, float sg_t, bool bgp) {
+    Sigmas r;
+    r.sh = fmaxf(sg_h, 0.f);
+    r.st = fmaxf(bgp ? 0.f : sg_t, 0.f);
+    if (bgp) r.st += 1e-6f;
+    r.s1 = bgp ? r.sh + 1e-6f : r.sh;
+    r.ss = r.sh + r.st;
+    return r;
 }
 
-// ================================================================================================
-// opacity and expected depth of the training step (DESIGN.md 4 "Opacity and expected depth", on the recorded samples)
-// ================================================================================================
-// stats[ray] = (acc_head, depth_head, acc_com, depth_com): acc = sum_FG w_i, depth = sum_FG w_i z_i over the step's final samples in
-// depth order, FG = every sample but the last when concate_bg, w the head image's (|d_head|) or the composite's (|d_torso|) weights.
-// One wave per ray, four rays per workgroup.  HIER = false: the form of composite_bwd_kernel (K = KL consecutive samples per lane,
-// lanes past n_coarse idle, the depths from the linspace); HIER = true: that of composite_bwd_hier_kernel (S = 64 K merged positions
-// through the inverse of the rank map, the depths z_all).  The weights are formed with the operations of weights_bwd_n / image_bwd
-// - expf, 1 - a + 1e-10, wave_excl_prod over the lanes' local products, the coarse form carrying the product across a lane's
-// positions (T *= v), the hierarchical one as T0 * pre - and the sigma fix-ups of the last sample; the blend's denominator shapes
-// colours, not weights, and the background colour is not read.  What dfn_composite_bwd_stats differentiates is what this writes.
-// ORDER of the sums: a lane adds its K positions in index order (p = 0; p += w, or p += w * z: a product, then a sum), then
-// wave_sum_xor (partners at XOR distance 32 ... 1).  No atomics, one writer per output: two runs give the same bits.
-template <int K, bool HIER>
-__device__ __forceinline__ void stats_weights(const float (&s)[K], const float (&dist)[K], const bool (&live)[K], int lane, float (&w)[K]) {
-    float e[K], a[K], v[K], pre[K];
-    float prod = 1.0f;
+// ---- the weights w_i = a_i T_i of one image (run_nerf_com_trainExpLater.py:169-179) over a ray, and their backward
+// The transmittance is a product over the lanes' local products, carried across a lane's positions as T0 * (product of the lane's
+// earlier positions); an idle position has a = 0, v = 1.
+template <int K> struct ImageW {
+    float e[K], a[K], v[K], T[K], w[K];
+};
+template <int K>
+__device__ __forceinline__ void image_weights(const float (&s)[K], const float (&dist)[K], const bool (&live)[K], int lane, ImageW<K>& W) {
+    float pre[K], prod = 1.0f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        e[k] = expf(-((fmaxf(s[k], 0.f) + 1e-6f) * dist[k]));
-        a[k] = live[k] ? 1.0f - e[k] : 0.f;
-        v[k] = live[k] ? 1.0f - a[k] + 1e-10f : 1.0f;
+        W.e[k] = expf(-((fmaxf(s[k], 0.f) + 1e-6f) * dist[k]));
+        W.a[k] = live[k] ? 1.0f - W.e[k] : 0.f;
+        W.v[k] = live[k] ? 1.0f - W.a[k] + 1e-10f : 1.0f;
         pre[k] = prod;
-        prod *= v[k];
+        prod *= W.v[k];
     }
-    float Tb = wave_excl_prod(K == 1 ? v[0] : prod, lane);
+    const float T0 = wave_excl_prod(prod, lane);          // transmittance in front of this lane's first position
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        if constexpr (HIER) {
-            w[k] = a[k] * (Tb * pre[k]);
-        } else {
-            w[k] = a[k] * Tb;
-            Tb *= v[k];
+        W.T[k] = T0 * pre[k];
+        W.w[k] = W.a[k] * W.T[k];
+    }
+}
+// ds_i = dL/d(s_i) given q_i = dL/dw_i: da_i = T_i q_i - (sum over the samples behind i of w q) / v_i, d a / d s = dist e.
+// The sum behind a position = the later lanes' (suf0) + this lane's later positions'.  HIER is the one place where the two steps are
+// not the same operations: the hierarchical step has always added suf0 + (0 + wq_2 + wq_1), the association K = 3 needs; the coarse
+// step carries suf0, suf0 + wq_1.  For K = 2 these are the same sums, but a starting 0 turns a -0 (suf0 and wq of an opaque ray under a
+// negative gradient: T = 0, q < 0) into +0, and the result's sign with it - and 64 + 64 and 128 both have K = 2.  For the same reason
+// K = 1 hands its single product to the scan, not 0 + it.
+template <int K, bool HIER>
+__device__ __forceinline__ void image_weights_bwd(const ImageW<K>& W, const float (&dist)[K], const float (&q)[K], int lane, float (&ds)[K]) {
+    float wq[K], sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        wq[k] = W.w[k] * q[k];
+        sum += wq[k];
+    }
+    const float suf0 = wave_suffix_sum_excl(K == 1 ? wq[0] : sum, lane);
+    float run = suf0, later = 0.f;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {
+        float behind = run;
+        if constexpr (HIER) behind = suf0 + later;
+        const float da = W.T[k] * q[k] - behind / W.v[k];
+        ds[k] = da * dist[k] * W.e[k];
+        run += wq[k];
+        later += wq[k];
+    }
+}
+// DN: dL/d|d| of one image = (1 / |d|) sum_s ds_s (s_s + 1e-6) (alpha_s = 1 - exp(-(s_s + 1e-6) dz_s |d|): the norm reaches the image
+// through dist only).  A lane adds its own positions in index order, wave_sum_xor adds the lanes
+template <int K>
+__device__ __forceinline__ float norm_grad(const float (&ds)[K], const float (&s)[K], const bool (&live)[K], float nrm) {
+    float p = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (live[k]) p += ds[k] * (fmaxf(s[k], 0.f) + 1e-6f);
+    return wave_sum_xor(p) / nrm;
+}
+
+// ---- the differentiation of the two images
+// raw outputs of a lane's samples (sigma_h, rgb_h, sigma_t, rgb_t), or the gradients on them
+template <int K> struct RawSamples {
+    float sg_h[K], ch[K][3], sg_t[K], ct[K][3];
+};
+// in: the raw outputs, the head colour of a background sample already the background's (bgp[k]); Gh / Gc: dL/d(rgb) of the head image
+// and of the composite (two: the composite exists).  d: dL/d(in).
+// STATS: the loss also reads stats = (acc_head, depth_head, acc_com, depth_com) of composite_stats_kernel, acc = sum_FG w_i, depth =
+// sum_FG w_i z_i.  q_i IS dL/dw_i, so the stats add [i in FG] (g_acc + g_depth z_i) to q of their image and nothing else: d sigma, the
+// blend's branches, the ReLU masks and d_norm follow through the same code.
+// DN: d_norm = (dL/d|d_head|, dL/d|d_torso|) of this ray, written by lane 0.
+template <int K, bool HIER, bool DN, bool STATS>
+__device__ __forceinline__ void two_images_bwd(const RawSamples<K>& in, const LaneSamples<K>& P, const bool (&bgp)[K], const float (&nrm)[2],
+                                               bool two, const float (&Gh)[3], const float (&Gc)[3], const float* d_stats, float* d_norm,
+                                               int lane, RawSamples<K>& d) {
+    Sigmas sg[K];
+    float qs[2][K], dist[K], q[K], ds[K];
+    ImageW<K> W;
+#pragma unroll
+    for (int k = 0; k < K; ++k) sg[k] = effective_sigmas(in.sg_h[k], in.sg_t[k], bgp[k]);
+    if constexpr (STATS) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) qs[b][k] = (P.live[k] && !bgp[k]) ? d_stats[2 * b] + d_stats[2 * b + 1] * P.z[k] : 0.f;
+    }
+    {   // head-only image: density s1, colour ch
+        float s1[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            s1[k] = sg[k].s1;
+            dist[k] = P.dz[k] * nrm[0];
+            q[k] = in.ch[k][0] * Gh[0] + in.ch[k][1] * Gh[1] + in.ch[k][2] * Gh[2];
+            if constexpr (STATS) q[k] += qs[0][k];
+        }
+        image_weights<K>(s1, dist, P.live, lane, W);
+        image_weights_bwd<K, HIER>(W, dist, q, lane, ds);
+        if constexpr (DN) {
+            const float g = norm_grad<K>(ds, s1, P.live, nrm[0]);
+            if (lane == 0) d_norm[0] = g;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            d.sg_h[k] = in.sg_h[k] > 0.f ? ds[k] : 0.f;
+            d.sg_t[k] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                d.ch[k][c] = bgp[k] ? 0.f : W.w[k] * Gh[c];
+                d.ct[k][c] = 0.f;
+            }
+        }
+    }
+    if (!two) return;
+    // composite image (run_nerf_com_trainExpLater.py:146-166): density ss = sh + st, colour ch wh + ct wt with wh = sh / den, wt = st /
+    // den, den = ss or, where both fields are empty, the constant 1e-4 (then the blend's weights do not depend on the densities)
+    float ss[K], den[K], wh[K], wt[K];
+    bool zero[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        ss[k] = sg[k].ss;
+        zero[k] = ss[k] == 0.f;
+        den[k] = zero[k] ? 1e-4f : ss[k];
+        wh[k] = sg[k].sh / den[k];
+        wt[k] = sg[k].st / den[k];
+        float cm[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cm[c] = in.ch[k][c] * wh[k] + in.ct[k][c] * wt[k];
+        q[k] = cm[0] * Gc[0] + cm[1] * Gc[1] + cm[2] * Gc[2];
+        if constexpr (STATS) q[k] += qs[1][k];
+        dist[k] = P.dz[k] * nrm[1];
+    }
+    image_weights<K>(ss, dist, P.live, lane, W);
+    image_weights_bwd<K, HIER>(W, dist, q, lane, ds);
+    if constexpr (DN) {
+        const float g = norm_grad<K>(ds, ss, P.live, nrm[1]);
+        if (lane == 0) d_norm[1] = g;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float gch = in.ch[k][0] * Gc[0] + in.ch[k][1] * Gc[1] + in.ch[k][2] * Gc[2];
+        const float gct = in.ct[k][0] * Gc[0] + in.ct[k][1] * Gc[1] + in.ct[k][2] * Gc[2];
+        const float dwh = W.w[k] * gch, dwt = W.w[k] * gct;
+        float dsh = ds[k] + dwh / den[k], dst = ds[k] + dwt / den[k];
+        if (!zero[k]) {
+            const float common = (dwh * sg[k].sh + dwt * sg[k].st) / (den[k] * den[k]);
+            dsh -= common;
+            dst -= common;
+        }
+        if (in.sg_h[k] > 0.f) d.sg_h[k] += dsh;
+        if (in.sg_t[k] > 0.f && !bgp[k]) d.sg_t[k] += dst;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (!bgp[k]) d.ch[k][c] += W.w[k] * Gc[c] * wh[k];
+            d.ct[k][c] += W.w[k] * Gc[c] * wt[k];
         }
     }
 }
-template <int K, bool HIER, bool RAYS>
-__global__ __launch_bounds__(256) void composite_stats_kernel(const CompositeStatsArgs A) {
-    constexpr int S = 64 * K;
-    __shared__ unsigned char inv_s[4][HIER ? S : 4];
+
+// ---- the kernels
+// a sample's eight floats: the hierarchical step moves them as two float4 (its rows are gathered through ev), the coarse one as scalars
+template <bool VEC> __device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+    if constexpr (VEC) {
+        const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[j];
+    }
+}
+template <bool VEC> __device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+    if constexpr (VEC) {
+        ((float4*)p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+        ((float4*)p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p[j] = v[j];
+    }
+}
+// dsamples = dL/d(samples) from dL/d(rgb_head), dL/d(rgb_com) [and d_stats]; [d_norm].  RAYS: the norms from the directions of row
+// `ray`, the coarse depths between that ray's bounds when given, the background row of a supplied ray is the ray's own
+template <int K, bool HIER, bool RAYS, bool DN, bool STATS>
+__global__ __launch_bounds__(HIER ? 256 : 1024) void composite_bwd_kernel(const CompositeBwdArgs A) {
+    static_assert(RAYS || !DN, "d_norm belongs to the rays forms");
+    composite_zero_fill(A);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long ray = (long)blockIdx.x * 4 + wv;
     if (ray >= A.frame.ray_count) return;
     const DfnFrame& F = A.frame;
-    const int NC = HIER ? S : F.n_coarse;             // samples of the ray
+    const int pix = RAYS ? (int)ray : A.pix_index ? A.pix_index[ray] : F.ray_begin + (int)ray;
     float nrm[2];
-    float nf[2] = {F.z_near, F.z_far};
-    if constexpr (RAYS) {
-        ray_row_norms(A.rays, ray, nrm);
-        if (A.bounds) {
-            nf[0] = A.bounds[ray * 2];
-            nf[1] = A.bounds[ray * 2 + 1];
-        }
-    } else {
-        // geometry (same arithmetic as the forward and the backward kernels)
-        const int pix = A.pix_index[ray];
-        const int y = pix / F.W, x = pix - y * F.W;
-        const float dx = __fdiv_rn(__fsub_rn((float)x, F.cx), F.focal), dy = __fdiv_rn(-__fsub_rn((float)y, F.cy), F.focal);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float* P = b ? F.pose_body : F.pose;
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, P[4 * k]), __fmul_rn(dy, P[4 * k + 1])),
-                                          __fmul_rn(-1.0f, P[4 * k + 2]));
-                acc = __fadd_rn(acc, __fmul_rn(d, d));
-            }
-            nrm[b] = sqrtf(acc);
-        }
-    }
-    unsigned char* inv = inv_s[wv];
-    if constexpr (HIER) {      // inverse of the rank map: merged position -> evaluation index
-#pragma unroll
-        for (int m = 0; m < K; ++m) inv[A.ranks[ray * S + lane + 64 * m]] = (unsigned char)(lane + 64 * m);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    const float step = coarse_step(NC);
-    auto zval = [&](int i) { return coarse_depth(nf[0], nf[1], coarse_t(step, NC, i)); };
+    if constexpr (RAYS) ray_row_norms(A.rays, ray, nrm);
+    else pinhole_norms(F, pix, nrm);
+    LaneSamples<K> P;
+    lane_samples<K, HIER, RAYS>(A, ray, lane, wv, P);
     const bool cbg = F.concate_bg != 0;
-    bool live[K], fg[K];
-    float z[K], s1[K], ss[K], dist_h[K], dist_c[K];
+    float Gh[3], Gc[3], bgc[3] = {0.f, 0.f, 0.f}, gs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        Gh[c] = A.d_rgb_head[ray * 3 + c];
+        Gc[c] = A.d_rgb_com ? A.d_rgb_com[ray * 3 + c] : 0.f;
+        if (cbg) bgc[c] = A.bg_u8 ? __fdiv_rn((float)A.bg_u8[(size_t)pix * 3 + c], 255.0f) : A.bg_f32[(size_t)pix * 3 + c];
+    }
+    if constexpr (STATS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gs[j] = A.d_stats[ray * 4 + j];
+    }
+    RawSamples<K> in, d;
+    bool bgp[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int i = lane * K + k;
-        live[k] = i < NC;
-        const int ii = live[k] ? i : NC - 1;
-        const bool last = ii == NC - 1;
-        float dz;
-        int ev = ii;
-        if constexpr (HIER) {
-            ev = inv[ii];
-            z[k] = A.z_all[ray * S + ii];
-            dz = last ? F.last_dist : __fsub_rn(A.z_all[ray * S + ii + 1], z[k]);
-        } else {
-            z[k] = zval(ii);
-            dz = last ? F.last_dist : __fsub_rn(zval(ii + 1), z[k]);
+        float v[8];
+        load8<HIER>(A.samples + ((size_t)ray * P.n + P.ev[k]) * 8, v);
+        bgp[k] = cbg && P.last[k];
+        in.sg_h[k] = v[0];
+        in.sg_t[k] = v[4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            in.ch[k][c] = bgp[k] ? bgc[c] : v[1 + c];
+            in.ct[k][c] = v[5 + c];
         }
-        const float* sm = A.samples + ((size_t)ray * NC + ev) * 8;
-        const float sh = fmaxf(sm[0], 0.f);
-        float st = fmaxf((cbg && last) ? 0.f : sm[4], 0.f);
-        if (cbg && last) st += 1e-6f;
-        s1[k] = (cbg && last) ? sh + 1e-6f : sh;
-        ss[k] = sh + st;
-        dist_h[k] = dz * nrm[0];
-        dist_c[k] = dz * nrm[1];
-        fg[k] = live[k] && !(cbg && last);
+    }
+    two_images_bwd<K, HIER, DN, STATS>(in, P, bgp, nrm, F.fields == 2, Gh, Gc, gs, DN ? A.d_norm + ray * 2 : nullptr, lane, d);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (!P.live[k]) continue;
+        const float v[8] = {d.sg_h[k], d.ch[k][0], d.ch[k][1], d.ch[k][2], d.sg_t[k], d.ct[k][0], d.ct[k][1], d.ct[k][2]};
+        store8<HIER>(A.dsamples + ((size_t)ray * P.n + P.ev[k]) * 8, v);
+    }
+}
+// stats[ray] = (acc_head, depth_head, acc_com, depth_com): acc = sum_FG w_i, depth = sum_FG w_i z_i over the step's final samples in
+// depth order, FG = every sample but the last when concate_bg, w the head image's (|d_head|) or the composite's (|d_torso|) weights
+// (DESIGN.md 4 "Opacity and expected depth").  The samples and the weights are the backward's own functions; the blend's denominator
+// shapes colours, not weights, and the background colour is not read.  What dfn_composite_bwd_stats differentiates is what this writes.
+// ORDER of the sums: a lane adds its K positions in index order (p = 0; p += w, or p += w * z: a product, then a sum), then
+// wave_sum_xor (partners at XOR distance 32 ... 1).  No atomics, one writer per output: two runs give the same bits.
+template <int K, bool HIER, bool RAYS>
+__global__ __launch_bounds__(256) void composite_stats_kernel(const CompositeStatsArgs A) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long ray = (long)blockIdx.x * 4 + wv;
+    if (ray >= A.frame.ray_count) return;
+    const DfnFrame& F = A.frame;
+    float nrm[2];
+    if constexpr (RAYS) ray_row_norms(A.rays, ray, nrm);
+    else pinhole_norms(F, A.pix_index[ray], nrm);
+    LaneSamples<K> P;
+    lane_samples<K, HIER, RAYS>(A, ray, lane, wv, P);
+    const bool cbg = F.concate_bg != 0;
+    bool fg[K];
+    float s[2][K], dist[2][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const float* sm = A.samples + ((size_t)ray * P.n + P.ev[k]) * 8;
+        const bool bgp = cbg && P.last[k];
+        const Sigmas sg = effective_sigmas(sm[0], sm[4], bgp);
+        s[0][k] = sg.s1;
+        s[1][k] = sg.ss;
+        dist[0][k] = P.dz[k] * nrm[0];
+        dist[1][k] = P.dz[k] * nrm[1];
+        fg[k] = P.live[k] && !bgp;
     }
     float out[4];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-        float w[K];
-        if (b == 0) stats_weights<K, HIER>(s1, dist_h, live, lane, w);
-        else stats_weights<K, HIER>(ss, dist_c, live, lane, w);
+        ImageW<K> W;
+        image_weights<K>(s[b], dist[b], P.live, lane, W);
         float pa = 0.f, pd = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (fg[k]) {
-                pa += w[k];
-                pd += w[k] * z[k];
+                pa += W.w[k];
+                pd += W.w[k] * P.z[k];
             }
         out[2 * b] = wave_sum_xor(pa);
         out[2 * b + 1] = wave_sum_xor(pd);
@@ -735,25 +458,53 @@ __global__ __launch_bounds__(256) void composite_stats_kernel(const CompositeSta
     const float o = lane == 0 ? out[0] : lane == 1 ? out[1] : lane == 2 ? out[2] : out[3];
     if (lane < 4) A.stats[ray * 4 + lane] = o;
 }
-template <bool RAYS>
-static hipError_t launch_composite_stats_t(const CompositeStatsArgs& A, hipStream_t st) {
-    const int blocks = (A.frame.ray_count + 3) / 4;
-    const int nc = A.frame.n_coarse, K = (64 + A.frame.n_fine) / 64;
-    if (A.frame.n_fine) {
-        if (K == 2) hipLaunchKernelGGL((composite_stats_kernel<2, true, RAYS>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_stats_kernel<3, true, RAYS>), dim3(blocks), dim3(256), 0, st, A);
-    } else {
-        if (nc == 128) hipLaunchKernelGGL((composite_stats_kernel<2, false, RAYS>), dim3(blocks), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((composite_stats_kernel<1, false, RAYS>), dim3(blocks), dim3(256), 0, st, A);
+
+// ---- one dispatch
+// THE count rule of the family: 32 / 64 (K = 1) or 128 (K = 2) coarse samples and no fine ones, or 64 coarse + 64 (K = 2) or 128 (K = 3)
+// fine ones; two fields wherever a rays row or the stats' two pairs are involved.  -1: refused
+enum SampleForm { COARSE_1, COARSE_2, HIER_2, HIER_3 };
+static int sample_form(const DfnFrame& F, bool two_fields_only) {
+    if (two_fields_only && F.fields != 2) return -1;
+    if (F.n_fine == 0) return F.n_coarse == 128 ? COARSE_2 : (F.n_coarse == 64 || F.n_coarse == 32) ? COARSE_1 : -1;
+    if (F.n_coarse != 64) return -1;
+    return F.n_fine == 64 ? HIER_2 : F.n_fine == 128 ? HIER_3 : -1;
+}
+typedef void (*CompositeBwdKernel)(const CompositeBwdArgs);
+template <bool RAYS, bool DN, bool STATS> static CompositeBwdKernel composite_bwd_of(int form) {
+    switch (form) {
+    case COARSE_1: return composite_bwd_kernel<1, false, RAYS, DN, STATS>;
+    case COARSE_2: return composite_bwd_kernel<2, false, RAYS, DN, STATS>;
+    case HIER_2: return composite_bwd_kernel<2, true, RAYS, DN, STATS>;
+    default: return composite_bwd_kernel<3, true, RAYS, DN, STATS>;
     }
+}
+// the block says which form it is: rays given = on caller-supplied rays, d_norm given = with the norm gradients (rays only), d_stats
+// given = the loss reads the stats; n_fine > 0 = the hierarchical step
+hipError_t launch_composite_bwd(const CompositeBwdArgs& A, hipStream_t st) {
+    const bool rays = A.rays, dn = A.d_norm, stats = A.d_stats;
+    const int form = sample_form(A.frame, rays || stats);
+    if (form < 0 || (dn && !rays)) return hipErrorInvalidValue;
+    const CompositeBwdKernel kernel = dn     ? (stats ? composite_bwd_of<true, true, true>(form) : composite_bwd_of<true, true, false>(form))
+                                      : rays ? (stats ? composite_bwd_of<true, false, true>(form) : composite_bwd_of<true, false, false>(form))
+                                             : (stats ? composite_bwd_of<false, false, true>(form) : composite_bwd_of<false, false, false>(form));
+    hipLaunchKernelGGL(kernel, dim3((A.frame.ray_count + 3) / 4), dim3(256), 0, st, A);
     return hipGetLastError();
 }
+typedef void (*CompositeStatsKernel)(const CompositeStatsArgs);
+template <bool RAYS> static CompositeStatsKernel composite_stats_of(int form) {
+    switch (form) {
+    case COARSE_1: return composite_stats_kernel<1, false, RAYS>;
+    case COARSE_2: return composite_stats_kernel<2, false, RAYS>;
+    case HIER_2: return composite_stats_kernel<2, true, RAYS>;
+    default: return composite_stats_kernel<3, true, RAYS>;
+    }
+}
 hipError_t launch_composite_stats(const CompositeStatsArgs& A, hipStream_t st) {
-    const bool hier = A.frame.n_fine != 0;
-    if (!A.samples || !A.stats || A.frame.fields != 2 || !stats_counts_ok(A.frame, hier) || (hier && (!A.z_all || !A.ranks)) ||
-        (!A.rays == !A.pix_index))
-        return hipErrorInvalidValue;
-    return A.rays ? launch_composite_stats_t<true>(A, st) : launch_composite_stats_t<false>(A, st);
+    const int form = sample_form(A.frame, true);
+    if (form < 0 || !A.samples || !A.stats || (A.frame.n_fine && (!A.z_all || !A.ranks)) || (!A.rays == !A.pix_index)) return hipErrorInvalidValue;
+    const CompositeStatsKernel kernel = A.rays ? composite_stats_of<true>(form) : composite_stats_of<false>(form);
+    hipLaunchKernelGGL(kernel, dim3((A.frame.ray_count + 3) / 4), dim3(256), 0, st, A);
+    return hipGetLastError();
 }
 
 // ================================================================================================

@@ -1,6 +1,6 @@
 """GPU tests of the fused training step on CALLER-SUPPLIED rays: dfn_train_rays_fwd / dfn_train_rays_fwd_hier (the training forwards
 render_kernel<TIER | TIER_RAYS, true, TRAIN>: csrc/dfn_render_variant.hip built as dfn_render_*_rays_train) and
-dfn_composite_bwd_rays_z / dfn_composite_bwd_hier_rays_z (composite_bwd_kernel<KL, RAYS>, composite_bwd_hier_kernel<K, RAYS>), through
+dfn_composite_bwd_rays_z / dfn_composite_bwd_hier_rays_z (the RAYS instantiations of composite_bwd_kernel, coarse and hierarchical), through
 training.render_train(rays=, bounds=).
 
   1. pinhole rays supplied = the plain step, bit for bit: images, raw samples, recorded activations and ReLU masks, every decoder
